@@ -31,9 +31,16 @@ one full iteration (include/forceatlas.hpp:146-270); multi-GPU = row shards + on
 RCCL all-gather of the coordinates per iteration.  --workload c3 (configs[2]):
 the multilevel step on the 1M-id R-MAT's LCC.
 
-Also reported: edges/s, the dominant kernel's roofline (HIP events on the
-launching stream), end-to-end device partition / P^T A P / embed times, and a CPU
-baseline (the oracle, rank 0, N = 1 only, bounded sample).
+A plain run sets up, warms up, times the K steps and prints one JSON line: the
+headline rate, ms_per_step, edges/s and the dominant kernels' rooflines from HIP
+events recorded on the launching stream during the timed steps themselves.
+--dump-outputs DIR then writes the coordinates the timed call returned as
+DIR/X.npy (float64; a fixed, seeded sample of the rows where the whole array
+exceeds DUMP_BYTES), identical from run to run for the same arguments.
+
+--full adds everything that takes work of its own: P^T A P per level and the
+end-to-end device embed, the measured HBM traffic looked up in the committed PMC
+passes, and a CPU baseline (the oracle, rank 0, N = 1 only, bounded sample).
 """
 import argparse
 import glob
@@ -88,15 +95,39 @@ def parse():
     ap.add_argument("--mode", choices=["strict", "fast"], default="strict",
                     help="c2 only: fast mode is re-associated (not parity-valid)")
     ap.add_argument("--levels", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: end-to-end embed "
+                         "(with P^T A P), PMC traffic lookup, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's coordinates to DIR/X.npy (float64)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="c3/c4: skip the timed partition::embed over the whole hierarchy")
+                    help="--full, c3/c4: skip the timed partition::embed over the whole hierarchy")
     ap.add_argument("--partition-host", action="store_true",
                     help="c3/c4: also time the library's host partition (minutes at c4)")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, check the process group and exit (no GPU work)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs: the most one array may take on disk
+DUMP_SEED = 20240607    # the row sample of a larger array (independent of --seed)
+
+
+def dump_outputs(dirpath, X):
+    """--dump-outputs: what a caller of the timed path receives, the (n, dim) fp64
+    coordinates on the device, as DIR/X.npy.  An array above DUMP_BYTES is cut to a
+    fixed, seeded sample of its rows (ascending), the same rows in every run."""
+    import torch
+    n, dim = X.shape
+    rows = DUMP_BYTES // (8 * dim)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, rows, replace=False))
+        X = X[torch.from_numpy(idx).to(X.device)]
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "X.npy"), X.cpu().numpy().astype(np.float64, copy=False))
 
 
 def log(rank, *a):
@@ -397,11 +428,14 @@ def run_multilevel(args, rank, world, local, dev):
                    for a, b in zip(hh, hier_full)), "device and host partition differ"
     log(rank, f"LCC n={n0} nnz={nnz0} (gen {t_gen:.1f}s), device partition {t_part:.1f}s, "
               f"levels {[h[2] for h in hier_full]}")
-    t0 = time.perf_counter()
-    As = [L]
-    for PT in hier:
-        As.append(ctx.ptap(As[-1], PT))
-    t_ptap = time.perf_counter() - t0
+    end_to_end = args.full and rank == 0 and world == 1 and not args.no_end_to_end
+    t_ptap = None
+    if end_to_end:  # the coarse operators: only the whole-hierarchy embed reads them
+        t0 = time.perf_counter()
+        As = [L]
+        for PT in hier:
+            As.append(ctx.ptap(As[-1], PT))
+        t_ptap = time.perf_counter() - t0
     PT = hier[0]
     m = PT[2]
     vA = ge.vertex_of(PT)
@@ -467,10 +501,13 @@ def run_multilevel(args, rank, world, local, dev):
     # x write 24 B per row, 12 B per CSR entry (int32 index + fp64 weight)
     att_bytes = 12 * att_entries + 52 * att_rows
     att_gbs = att_bytes / (att_ms * 1e-3) / 1e9 if att_ms > 0 else 0.0
-    att_traffic, att_src = pmc_traffic_per_launch("FamlRows", args.workload)
+    traffic_of = pmc_traffic_per_launch if args.full else (lambda *a: (None, None))
+    att_traffic, att_src = traffic_of("FamlRows", args.workload)
     rep_kernel = "faml_big_repulse" if os.environ.get("GE_FAML_SYM") == "0" else "faml_sym_repulse"
-    traffic, traffic_src = pmc_traffic_per_launch(rep_kernel, args.workload)
+    traffic, traffic_src = traffic_of(rep_kernel, args.workload)
     finite = bool(torch.isfinite(X).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, X)
     sizes = np.diff(PT[0]).astype(np.float64)
     pairs = float((sizes * (sizes - 1)).sum())
     its = args.steps / elapsed
@@ -550,14 +587,14 @@ def run_multilevel(args, rank, world, local, dev):
         p.close()
     if comm is not None:
         comm.close()
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if end_to_end:
         t0 = time.perf_counter()
         Xe = ctx.embed(As, hier, args.dim, seed=args.seed)
         result["embed_seconds_end_to_end"] = time.perf_counter() - t0
         result["embed_finite"] = bool(np.isfinite(Xe).all())
         result["pipeline_seconds_device"] = (t_part + t_ptap +
                                              result["embed_seconds_end_to_end"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_ml(L, PT, vA, cA, rA, args.dim,
                                                  args.cpu_baseline_seconds, rank)
         result["vs_cpu_baseline"] = its / result["cpu_baseline"]["value"]
@@ -616,8 +653,11 @@ def run_single_level(args, rank, world, local, dev):
     # plan over every row (one rank), the ordered-pair kernel on a row shard or FAST
     sym = (args.mode == "strict" and world == 1 and os.environ.get("GE_FA_SYM", "") != "0")
     rep_kernel = "faml_sym_repulse" if sym else "fa_repulse_%s" % args.mode
-    traffic, traffic_src = pmc_traffic_per_launch(rep_kernel, "c2")
-    att_traffic, att_src = pmc_traffic_per_launch("FaRows", "c2")
+    traffic_of = pmc_traffic_per_launch if args.full else (lambda *a: (None, None))
+    traffic, traffic_src = traffic_of(rep_kernel, "c2")
+    att_traffic, att_src = traffic_of("FaRows", "c2")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, buf[0][:n])
     result = {
         "metric": METRIC, "value": its, "unit": "iterations/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -654,7 +694,7 @@ def run_single_level(args, rank, world, local, dev):
         "ranks": dict(comm_record(comm, world), per_rank_seconds=per_rank,
                       rows_per_rank=[b - a for a, b in shards]),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_fa(A, X0, args.cpu_baseline_seconds, rank)
         result["vs_cpu_baseline"] = its / result["cpu_baseline"]["value"]
     plan.close()

@@ -7,7 +7,8 @@
 #   tests            the whole -m gpu suite                  -> tests.log
 #   tests:EXPR       a -k selection of it                    -> tests.log
 #   smoke            __graft_entry__.smoke()                 -> smoke.log
-#   bench:W[:ARGS]   bench.py --workload W --steps 20 --warmup 5 [ARGS, commas = spaces]
+#   bench:W[:ARGS]   bench.py --full --workload W --steps 20 --warmup 5 [ARGS, commas =
+#                    spaces]: the headline plus end-to-end embed and CPU baseline
 #                                                            -> bench_W.json
 #   trace:W          rocprofv3 --kernel-trace --stats of bench W (steps 20, no baseline)
 #                                                            -> rocprof_kernel_stats_W.csv
@@ -47,7 +48,7 @@ for step in "$@"; do
         || fail "$step" $? $OUT/smoke.log
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 900 python -u bench.py --workload $a --steps 20 --warmup 5 ${b//,/ } \
+      timeout -k 10 900 python -u bench.py --full --workload $a --steps 20 --warmup 5 ${b//,/ } \
         > $OUT/bench_$a.json 2> $OUT/bench_$a.err || fail "$step" $? $OUT/bench_$a.err
       cat $OUT/bench_$a.json ;;
     trace)
