@@ -1,9 +1,9 @@
 // ge_oracle.cpp -- CPU restatement of graph-embed's hot path.
 //
 // TEST INFRASTRUCTURE ONLY (see ge_oracle.h): the checker for the HIP path and
-// the timed CPU baseline.  PARITY UNPINNED against the reference build (the
-// reference needs the absent linalgcpp and ships no fixtures); cross-checked
-// against tests/pyref.py.
+// the timed CPU baseline.  Pinned bit for bit to the reference's own translation
+// units (oracle/_ref/ge_ref, tests/test_reference.py) and cross-checked against
+// tests/pyref.py; linalgcpp's operations (P^T A P) are outside that pin.
 //
 // Build: see oracle/Makefile.  Compiled with -O2 -ffp-contract=off so every
 // multiply and add rounds separately, as in the reference's x86-64 -O2 build.

@@ -5,14 +5,15 @@
  * cpu_baseline leg of bench.py may load liboracle.so, and only as the checker /
  * the timed CPU baseline -- never as the product path.
  *
- * PARITY UNPINNED against the reference itself: the reference cannot be built
- * here (its only dependency, linalgcpp, is not vendored and not installed, and
- * the rules forbid a stand-in header), and it ships no tests, fixtures or golden
- * vectors.  This file is an independent restatement of the
- * reference algorithm, written from the reference source read as text, with each
- * function citing the reference lines it follows.  It is cross-checked bit-for-bit
- * against a second, independent pure-Python restatement (tests/pyref.py) on small
- * cases.
+ * This file is an independent restatement of the reference algorithm, written
+ * from the reference source read as text, with each function citing the
+ * reference lines it follows.  It is pinned bit for bit to the reference's own
+ * translation units, which oracle/Makefile builds into oracle/_ref/ge_ref against
+ * the linalgcpp subset in graph-embed_amd/compat/ (tests/test_reference.py), and
+ * cross-checked against a second, independent pure-Python restatement
+ * (tests/pyref.py).  Outside that pin: linalgcpp's own operations (P^T A P
+ * keeps its dense-definition test) -- the reference ships no tests, fixtures or
+ * golden vectors of its own.
  *
  * Conventions (all pinned here; the reference leaves them to random_device /
  * the absent linalgcpp):

@@ -2,11 +2,12 @@
 
     python tests/golden/make_golden.py
 
-The reference cannot be built here (linalgcpp is absent and a stand-in is not
-allowed) and ships no fixtures, so these vectors are produced by the oracle
+The reference ships no fixtures, so these vectors are produced by the oracle
 (oracle/ge_oracle.cpp), which tests/test_oracle.py cross-checks bit for bit
-against the independent pure-Python restatement tests/pyref.py.  Parity of the
-fixtures with the reference itself is therefore UNPINNED (Oracle).
+against the independent pure-Python restatement tests/pyref.py and
+tests/test_reference.py pins to the reference's own translation units
+(Oracle).  The fixtures recorded from the reference itself are the
+ref_* files (make_ref_fixtures.py).
 
 Every fixture stores its inputs (graph, seeds, parameters) with the outputs, so
 the GPU tests need nothing but the .npz file.

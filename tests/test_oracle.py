@@ -1,9 +1,11 @@
 """The oracle (oracle/ge_oracle.cpp) against the independent pure-Python
 restatement (tests/pyref.py) and against the committed golden fixtures.
 
-No reference tests or fixtures exist and the reference
-cannot be built here, so these two restatements pin each other; parity with the
-reference binary itself is unpinned.
+The reference ships no tests or fixtures; these two
+restatements pin each other here.  The pin to the reference's own code -- its
+translation units built into oracle/_ref/ge_ref -- is tests/test_reference.py
+(DESIGN.md section 3).  linalgcpp's operations are outside that pin, so P^T A P
+keeps its dense-definition test below.
 """
 import numpy as np
 import pytest
