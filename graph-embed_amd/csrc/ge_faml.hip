@@ -719,6 +719,7 @@ struct ge_faml_plan {
   const double* dx = nullptr;
   ge::FaConst c{};
   int ns = 0, nm = 0, nl = 0, nhuge = 0;
+  int res_cap = 0, census[4] = {0, 0, 0, 0};  // aggregates: small, mid, large-resident, streamed
   size_t off_m = 0, off_l = 0;
   ge::DevBuf<int> pos, order, beg, rows, erows, queue, huge, ecode;
   ge::RowClasses ecls;
@@ -787,7 +788,10 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   GE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   const double per_cu = W / std::max(cus, 1);
   int res_cap = (int)std::sqrt(per_cu / 4.0);  // largest aggregate kept resident
+  // GE_FAML_RES_CAP: the cap itself (tests: the large-resident class on small inputs)
+  if (const char* e = std::getenv("GE_FAML_RES_CAP")) res_cap = std::atoi(e);
   res_cap = std::max(256, std::min(res_cap, large_cap(dim)));
+  pl->res_cap = res_cap;
 
   std::vector<int> small, mid, large, big;
   for (int a : aggs) {
@@ -798,6 +802,10 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
     else if (s <= res_cap) large.push_back(a);
     else big.push_back(a);
   }
+  pl->census[0] = (int)small.size();
+  pl->census[1] = (int)mid.size();
+  pl->census[2] = (int)large.size();
+  pl->census[3] = (int)big.size() + (int)split.size();
   auto by_size = [&](int x, int y) {
     const int sx = h_pt_ip[x + 1] - h_pt_ip[x], sy = h_pt_ip[y + 1] - h_pt_ip[y];
     return sx != sy ? sx > sy : x < y;
@@ -1565,6 +1573,21 @@ int ge_faml_plan_schedule(ge_faml_plan* pl, int* sweeps, int* banded, int* row_b
     *banded = 0;  // bands were removed in round 5 (the ABI keeps the field)
     *row_blocks = pl->rows_mode;
     *units = pl->nunits;
+  });
+}
+
+int ge_faml_plan_classes(ge_faml_plan* pl, int* res_cap, int* aggregates, int* blocks,
+                          int* rows) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && res_cap && aggregates && blocks && rows, "null argument");
+    *res_cap = pl->res_cap;
+    for (int k = 0; k < 4; ++k) aggregates[k] = pl->census[k];
+    blocks[0] = pl->ns;
+    blocks[1] = pl->nm;
+    blocks[2] = pl->nl;
+    const ge::RowClasses& rc = pl->ecls;
+    const int r[6] = {rc.ntiles, rc.nheavy, rc.nseg, rc.seg_mode, rc.nearly, rc.nseg_early};
+    for (int k = 0; k < 6; ++k) rows[k] = r[k];
   });
 }
 

@@ -114,6 +114,7 @@ _SIGS = {
     "ge_faml_plan_repulse_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _ip,
                                                ctypes.POINTER(ctypes.c_double)]),
     "ge_faml_plan_schedule": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip]),
+    "ge_faml_plan_classes": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip]),
     "ge_faml_plan_rows_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _ip,
                                             ctypes.POINTER(ctypes.c_longlong),
                                             ctypes.POINTER(ctypes.c_longlong)]),
@@ -596,6 +597,20 @@ class FamlPlan:
         v = [ctypes.c_int() for _ in range(4)]
         _check(lib().ge_faml_plan_schedule(self.h, *[ctypes.byref(x) for x in v]))
         return dict(zip(("sweeps", "banded", "row_blocks", "units"), (x.value for x in v)))
+
+    def classes(self):
+        """The size class every aggregate took and the classes of the streamed members'
+        rows (ge_faml_plan_classes): res_cap; aggregates small / mid / large / streamed;
+        blocks_small / blocks_mid / blocks_large of the resident launches; ntiles, nheavy,
+        nseg, seg_mode, nearly, nseg_early of the rows (late heavy rows: nheavy - nearly)."""
+        cap = ctypes.c_int()
+        aggs, blocks, rows = (ctypes.c_int * 4)(), (ctypes.c_int * 3)(), (ctypes.c_int * 6)()
+        _check(lib().ge_faml_plan_classes(self.h, ctypes.byref(cap), aggs, blocks, rows))
+        out = {"res_cap": cap.value}
+        out.update(zip(("small", "mid", "large", "streamed"), aggs))
+        out.update(zip(("blocks_small", "blocks_mid", "blocks_large"), blocks))
+        out.update(zip(("ntiles", "nheavy", "nseg", "seg_mode", "nearly", "nseg_early"), rows))
+        return out
 
     def close(self):
         """Destroys the plan; raises GeError when the library reports a failure

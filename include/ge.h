@@ -163,6 +163,18 @@ int ge_faml_plan_rows_ms(ge_faml_plan* plan, double* ms_per_pass, int* passes,
  * one launch.  Diagnostics; the results do not depend on it. */
 int ge_faml_plan_schedule(ge_faml_plan* plan, int* sweeps, int* banded, int* row_blocks,
                           int* units);
+/* The size class every aggregate of the plan took and the kernels that run them.
+ * res_cap: the largest aggregate kept resident in LDS (GE_FAML_RES_CAP overrides the
+ * plan's rule; clamped to [256, the large kernel's capacity at this dim]).
+ * aggregates[4]: small (<= 64 members), mid (<= 256), large-resident (<= res_cap),
+ * streamed (a shard plan's split aggregates included).  blocks[3]: blocks of the
+ * small, mid and large resident launches.  rows[6]: the classes of the streamed
+ * members' CSR rows -- tiles, heavy rows, heavy-row segments, segment mode (0 whole
+ * rows, 1 binade sums, 2 stored terms), early heavy rows (the late ones are
+ * heavy - early), the early rows' segments.  Diagnostics; the results do not
+ * depend on it. */
+int ge_faml_plan_classes(ge_faml_plan* plan, int* res_cap, int* aggregates, int* blocks,
+                         int* rows);
 int ge_faml_plan_destroy(ge_faml_plan* plan);
 
 /* ---- coarsening hierarchy ----

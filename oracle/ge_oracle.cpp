@@ -288,18 +288,15 @@ int orc_force_atlas(int n, const int* I, const int* J, const double* D, int dim,
 // null).  Single-thread draw order of :340-360: aggregates ascending, members in
 // P_T row order, k ascending -> draw c*dim+k for P_T storage position c, whichever
 // aggregates are evaluated.
-int orc_force_atlas_ml_aggs(int n, const int* I, const int* J, const double* D, int m,
-                            const int* PI, const int* PJ, const int* vA, const double* cA,
-                            const double* rA, double* X, int dim, int iterations,
-                            unsigned seed, const orc_fa_params* pp, const int* aggs,
-                            int n_aggs, int nthreads) {
+// `draws`: the PI[m] * dim starting values in that layout.
+static int force_atlas_ml_draws(const int* I, const int* J, const double* D, int m,
+                                const int* PI, const int* PJ, const int* vA, const double* cA,
+                                const double* rA, double* X, int dim, int iterations,
+                                const double* draws, const orc_fa_params* pp, const int* aggs,
+                                int n_aggs, int nthreads) {
   if (dim < 1 || dim > kMaxDim) return 1;
   const orc_fa_params p = *pp;
   set_threads(nthreads);
-  (void)n;
-  const long long total = (long long)PI[m] * dim;
-  std::vector<double> draws(total);
-  orc_uniform_stream(seed, total, draws.data());
   const int na = aggs ? n_aggs : m;
   // Aggregates are independent (the reference's `omp parallel for` over them,
   // :340); inside one, the force rows of an iteration are independent too (each
@@ -409,6 +406,31 @@ int orc_force_atlas_ml_aggs(int n, const int* I, const int* J, const double* D, 
     if (PI[a + 1] - PI[a] < kInnerRows) run_agg(a, false);
   }
   return 0;
+}
+
+int orc_force_atlas_ml_aggs(int n, const int* I, const int* J, const double* D, int m,
+                            const int* PI, const int* PJ, const int* vA, const double* cA,
+                            const double* rA, double* X, int dim, int iterations,
+                            unsigned seed, const orc_fa_params* pp, const int* aggs,
+                            int n_aggs, int nthreads) {
+  if (dim < 1 || dim > kMaxDim) return 1;
+  (void)n;
+  const long long total = (long long)PI[m] * dim;
+  std::vector<double> draws(total);
+  orc_uniform_stream(seed, total, draws.data());
+  return force_atlas_ml_draws(I, J, D, m, PI, PJ, vA, cA, rA, X, dim, iterations, draws.data(),
+                              pp, aggs, n_aggs, nthreads);
+}
+
+// orc_force_atlas_ml with the starting values supplied: init[c*dim+k] for P_T
+// storage position c (the layout of the draw stream above).
+int orc_force_atlas_ml_init(int n, const int* I, const int* J, const double* D, int m,
+                            const int* PI, const int* PJ, const int* vA, const double* cA,
+                            const double* rA, double* X, int dim, int iterations,
+                            const double* init, const orc_fa_params* pp, int nthreads) {
+  (void)n;
+  return force_atlas_ml_draws(I, J, D, m, PI, PJ, vA, cA, rA, X, dim, iterations, init, pp,
+                              nullptr, 0, nthreads);
 }
 
 int orc_force_atlas_ml(int n, const int* I, const int* J, const double* D, int m,

@@ -78,6 +78,13 @@ int orc_force_atlas_ml(int n, const int* indptr, const int* indices, const doubl
                        const int* vertex_A, const double* coords_A, const double* r_A,
                        double* coords, int dim, int iterations, unsigned seed,
                        const orc_fa_params* p, int nthreads);
+/* The same with the starting values supplied instead of drawn: init[c*dim+k] for
+ * P_T storage position c (the layout of the draw stream). */
+int orc_force_atlas_ml_init(int n, const int* indptr, const int* indices, const double* data,
+                            int m, const int* pt_indptr, const int* pt_indices,
+                            const int* vertex_A, const double* coords_A, const double* r_A,
+                            double* coords, int dim, int iterations, const double* init,
+                            const orc_fa_params* p, int nthreads);
 
 /* ---- partition hierarchy (src/partitioner.cpp:1550-1893) ---- */
 typedef struct orc_hier orc_hier;

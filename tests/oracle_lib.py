@@ -60,6 +60,10 @@ def lib():
                                               ctypes.c_int, ctypes.c_int, ctypes.c_uint,
                                               ctypes.POINTER(FaParams), _i32p, ctypes.c_int,
                                               ctypes.c_int]
+        L.orc_force_atlas_ml_init.argtypes = [ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
+                                              _i32p, _i32p, _i32p, _f64p, _f64p, _f64p,
+                                              ctypes.c_int, ctypes.c_int, _f64p,
+                                              ctypes.POINTER(FaParams), ctypes.c_int]
         L.orc_partition.restype = ctypes.c_void_p
         L.orc_partition.argtypes = [ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_double,
                                     ctypes.c_int, ctypes.c_double, ctypes.c_int]
@@ -192,7 +196,9 @@ def force_atlas_ml_aggs(A, PT, vertex_A, coords_A, r_A, dim, aggs, iterations=10
 
 
 def force_atlas_ml(A, PT, vertex_A, coords_A, r_A, dim, iterations=100, seed=0, nthreads=0,
-                   **kw):
+                   init=None, **kw):
+    """init: the n * dim starting values, init[c*dim+k] for P_T storage position c
+    (the layout of uniform_stream(seed, n * dim), which is the default start)."""
     ip, ix, dx = _csr(A)
     pip = np.ascontiguousarray(PT[0], dtype=np.int32)
     pix = np.ascontiguousarray(PT[1], dtype=np.int32)
@@ -200,11 +206,15 @@ def force_atlas_ml(A, PT, vertex_A, coords_A, r_A, dim, iterations=100, seed=0, 
     m = len(pip) - 1
     X = np.zeros((n, dim))
     p = params(**kw)
-    rc = lib().orc_force_atlas_ml(n, ip, ix, dx, m, pip, pix,
-                                  np.ascontiguousarray(vertex_A, dtype=np.int32),
-                                  np.ascontiguousarray(coords_A, dtype=np.float64).reshape(-1),
-                                  np.ascontiguousarray(r_A, dtype=np.float64), X.reshape(-1), dim,
-                                  iterations, seed, ctypes.byref(p), nthreads)
+    args = (n, ip, ix, dx, m, pip, pix, np.ascontiguousarray(vertex_A, dtype=np.int32),
+            np.ascontiguousarray(coords_A, dtype=np.float64).reshape(-1),
+            np.ascontiguousarray(r_A, dtype=np.float64), X.reshape(-1), dim, iterations)
+    if init is None:
+        rc = lib().orc_force_atlas_ml(*args, seed, ctypes.byref(p), nthreads)
+    else:
+        start = np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
+        assert start.size == n * dim
+        rc = lib().orc_force_atlas_ml_init(*args, start, ctypes.byref(p), nthreads)
     assert rc == 0
     return X
 

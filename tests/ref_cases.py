@@ -203,6 +203,144 @@ def _m3():
                4, 31)
 
 
+# --------------------------------------------------------------------------
+# The multilevel layouts of tests/test_gpu_faml_paths.py: one per size class of
+# faml_plan_build (ge_faml.hip), fractional weights, and the domain-edge inputs.
+
+LARGE_SIZES = [1031, 700, 257, 90]  # LDS-resident one per block under GE_FAML_RES_CAP=4096
+LAYOUTS = {
+    # name: (sizes, P_T permutation seed, GE_FAML_RES_CAP or None)
+    "packed": (M1_SIZES, sum(M1_SIZES), None),
+    "large": (LARGE_SIZES, 7, "4096"),
+    "streamed": (M2_SIZES, 5, "256"),
+}
+ML_OPTIONS = dict(ks=0.2, ksmax=0.05, repel=1.5, attract=0.7, gravity=2.0, tolerate=0.5)
+TINY = 1e-70  # outside coord_ok (ge_math.hpp: |x| in [2^-200, 2^200] or 0)
+HUGE_W = 2.0 ** 61  # deg + 1 above weight_ok's 2^60
+
+
+@functools.lru_cache(maxsize=None)
+def layout_graph(layout):
+    """The unit-weight graph of a layout."""
+    sizes = LAYOUTS[layout][0]
+    n = sum(sizes)
+    if layout == "packed":  # M1's graph
+        return _canon(G.submatrix(G.rmat(n, 6 * n, seed=len(sizes)), np.arange(n)))
+    if layout == "large":
+        return _canon(G.rmat(n, 8 * n, seed=4))
+    # M2's graph: two hub rows longer than a row tile (512 entries)
+    return _canon(G.with_hubs(G.rmat(n, 10 * n, seed=11), [(3, 2000), (70, 3000)], seed=3))
+
+
+def ml_layout(layout, dim=3, iterations=3, seed=19, weighted=True, **kw):
+    A = layout_graph(layout)
+    if weighted:
+        A = symmetric_weights(A)
+    sizes, pt_seed, _ = LAYOUTS[layout]
+    return _ml(A, sizes, pt_seed, dim, iterations, seed, **kw)
+
+
+def internal_edges(case, a):
+    """(i, j, e): CSR entries e of member rows of aggregate a whose column is a member too,
+    as local member indices i < j."""
+    ip, ix = case["A"][0], case["A"][1]
+    PT, vA = case["PT"], case["vA"]
+    v = PT[1][PT[0][a]:PT[0][a + 1]]
+    local = {int(g): i for i, g in enumerate(v)}
+    out = []
+    for i, g in enumerate(v):
+        for e in range(ip[g], ip[g + 1]):
+            j = ix[e]
+            if vA[j] == a and local[int(j)] > i:
+                out.append((i, local[int(j)], e))
+    return out
+
+
+def internal_degree_plus_one(case, a):
+    """deg + 1 of the members of aggregate a as forceAtlasMultilevel counts it
+    (include/forceatlas.hpp:362-383, use_weights on): the weights of the row's entries
+    whose column lies in a, added in CSR order."""
+    ip, ix, dx = case["A"]
+    PT, vA = case["PT"], case["vA"]
+    out = []
+    for g in PT[1][PT[0][a]:PT[0][a + 1]]:
+        acc = 0.0
+        for e in range(ip[g], ip[g + 1]):
+            if vA[ix[e]] == a:
+                acc += dx[e]
+        out.append(acc + 1)
+    return np.array(out)
+
+
+def with_heavy_edges(case):
+    """One internal edge per aggregate with weight 2^61 in both directions: exactly two
+    members of the aggregate leave weight_ok(deg + 1), so fast and fallback tiles mix.
+    In the largest aggregate the two lie in different 64-row tiles, one of them in the
+    last tile (ragged where the size is no multiple of 64)."""
+    ip, ix, dx = case["A"]
+    dx = dx.copy()
+    PT = case["PT"]
+    sizes = np.diff(PT[0])
+    for a in range(len(sizes)):
+        edges = internal_edges(case, a)
+        if a == int(np.argmax(sizes)) and sizes[a] > 64:
+            last = (sizes[a] - 1) // 64
+            edges = [t for t in edges if t[1] // 64 == last and t[0] // 64 != last]
+            assert edges, "no internal edge into the last tile: change the permutation seed"
+        if not edges:
+            continue
+        i, j, e = edges[0]
+        gi, gj = PT[1][PT[0][a] + i], PT[1][PT[0][a] + j]
+        back = ip[gj] + int(np.flatnonzero(ix[ip[gj]:ip[gj + 1]] == gi)[0])
+        assert ix[e] == gj and ix[back] == gi
+        dx[e] = dx[back] = HUGE_W
+    return dict(case, A=(ip, ix, dx))
+
+
+def with_scaled_weights(case, factor):
+    ip, ix, dx = case["A"]
+    return dict(case, A=(ip, ix, dx * factor))
+
+
+# aggregates of each layout that take the coords_A edges: `tiny` get a 1e-70 component,
+# `origin` sits at 0, the two of `same` share their coordinates, `zero_r` has r_A = 0
+COARSE_EDGES = {
+    "packed": dict(tiny=(12, 7), origin=11, same=(13, 8), zero_r=10),
+    "large": dict(tiny=(0,), origin=3, same=(1, 2), zero_r=2),
+    "streamed": dict(tiny=(0,), origin=6, same=(4, 2), zero_r=3),
+}
+
+
+def edges_between(case, a, b):
+    ip, ix = case["A"][0], case["A"][1]
+    rows = np.repeat(np.arange(len(ip) - 1), np.diff(ip))
+    vA = case["vA"]
+    return int(((vA[rows] == a) & (vA[ix] == b)).sum())
+
+
+def with_coarse_edges(case, layout):
+    spec = COARSE_EDGES[layout]
+    cA, rA = case["cA"].copy(), case["rA"].copy()
+    for q, a in enumerate(spec["tiny"]):
+        cA[a, q % cA.shape[1]] = TINY
+    cA[spec["origin"]] = 0.0
+    cA[spec["same"][1]] = cA[spec["same"][0]]
+    rA[spec["zero_r"]] = 0.0
+    return dict(case, cA=cA, rA=rA)
+
+
+# --------------------------------------------------------------------------
+# the cases pinned to the reference itself
+
+M6_D1_SIZES = [1000, 257, 256, 65, 64, 30, 1]
+M6_D4_SIZES = [2048, 257, 65, 64, 1]  # the large kernel at its dim-4 capacity, resident side
+
+
+def _m6(dim, sizes):
+    n = sum(sizes)
+    return _ml(symmetric_weights(G.rmat(n, 6 * n, seed=dim)), sizes, dim, dim, 3, 23)
+
+
 ML_CASES = {
     "M1": _m1,
     "M2_d2": lambda: _m2(2, 1.0),
@@ -210,7 +348,16 @@ ML_CASES = {
     "M2_d2_repel": lambda: _m2(2, 1.5),
     "M2_d3_repel": lambda: _m2(3, 1.5),
     "M3": _m3,
+    "M4_options": lambda: ml_layout("large", **ML_OPTIONS),
+    "M4_nohubs_unweighted": lambda: ml_layout("streamed", nohubs=1, use_weights=0),
+    "M5_weight_edges": lambda: with_heavy_edges(ml_layout("streamed")),
+    "M5_coarse_edges": lambda: with_coarse_edges(ml_layout("packed"), "packed"),
+    "M6_d1": lambda: _m6(1, M6_D1_SIZES),
+    "M6_d4": lambda: _m6(4, M6_D4_SIZES),
 }
+# the GE_FAML_RES_CAP each case's size classes need (None: the plan's own rule)
+ML_RES_CAP = {"M4_options": "4096", "M4_nohubs_unweighted": "256", "M5_weight_edges": "256",
+              "M6_d1": "4096", "M6_d4": "4096"}
 ML_QUIRK = ("M1", "M2_d2", "M2_d3", "M2_d2_repel", "M2_d3_repel")  # must hold such an edge
 
 

@@ -7,6 +7,7 @@ import pytest
 
 import ge_amd as ge
 import graphs as G
+from faml_plan import assert_census, run_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -500,10 +501,14 @@ def _block_partition(n, sizes, seed=0):
 @pytest.mark.parametrize("sizes", [
     [1, 2, 3, 5, 8, 13, 21, 34, 64, 9],            # packed 64-lane blocks
     [65, 100, 256, 3, 200],                         # 256-member packs
-    [257, 1000, 4096, 17],                          # one aggregate per block, LDS-resident
-    [5000, 300, 40, 1],                             # streamed (> 4096) path
+    # above 256 members and streamed all the same: sum s^2 is too small to lift res_cap
+    # off 256 (the census below says so); the LDS-resident large class, one aggregate per
+    # block, is run by test_gpu_faml_paths.py under GE_FAML_RES_CAP
+    [257, 1000, 4096, 17],
+    [5000, 300, 40, 1],                             # streamed path
 ])
-def test_faml_size_classes(ctx, oracle, sizes):
+def test_faml_size_classes(ctx, oracle, monkeypatch, sizes):
+    monkeypatch.delenv("GE_FAML_RES_CAP", raising=False)
     n = sum(sizes)
     A = G.submatrix(G.rmat(n, 6 * n, seed=len(sizes)), np.arange(n))
     PT = _block_partition(n, sizes, seed=n)
@@ -515,6 +520,12 @@ def test_faml_size_classes(ctx, oracle, sizes):
     want = oracle.force_atlas_ml(A, PT, vA, cA, rA, 3, iterations=it, seed=31)
     got = ctx.force_atlas_ml(A, PT, vA, cA, rA, 3, iterations=it, seed=31)
     assert np.array_equal(got, want)
+    # the census of the same level as a plan: every aggregate in the class the rule implies
+    planned, cls, _ = run_plan(ctx, dict(A=A, PT=PT, vA=vA, cA=cA, rA=rA, dim=3, iterations=it,
+                                         seed=31, kw={}))
+    assert_census(cls, sizes, 3)
+    assert cls["small"] + cls["mid"] + cls["large"] + cls["streamed"] == m
+    assert np.array_equal(planned, want)
 
 
 @pytest.mark.parametrize("R,U,tiles,segs,repel", [
@@ -554,6 +565,7 @@ def test_faml_early_heavy_row_chains(ctx, oracle, monkeypatch, dim):
     takes the other heavy rows' segments; the short chains follow it.  Two early rows
     (~12 000 and ~9 000 entries) and a later heavy row (~5 000), tiles forced."""
     monkeypatch.setenv("GE_ROWS_TILES", "1")
+    monkeypatch.delenv("GE_FAML_RES_CAP", raising=False)
     sizes = [12000, 3000, 2000, 300]
     n = sum(sizes)
     A = G.with_hubs(G.rmat(n, 8 * n, seed=23), [(5, 12000), (600, 9000), (40, 5000)], seed=dim)
@@ -567,6 +579,12 @@ def test_faml_early_heavy_row_chains(ctx, oracle, monkeypatch, dim):
     want = oracle.force_atlas_ml(A, PT, vA, cA, rA, dim, iterations=3, seed=29)
     got = ctx.force_atlas_ml(A, PT, vA, cA, rA, dim, iterations=3, seed=29)
     assert np.array_equal(got, want)
+    # the census of the same level as a plan: early and late heavy rows and tiles all ran
+    planned, cls, _ = run_plan(ctx, dict(A=A, PT=PT, vA=vA, cA=cA, rA=rA, dim=dim, iterations=3,
+                                         seed=29, kw={}))
+    assert_census(cls, sizes, dim)
+    assert cls["nearly"] >= 2 and cls["nheavy"] - cls["nearly"] >= 1 and cls["ntiles"] > 0, cls
+    assert np.array_equal(planned, want)
 
 
 @pytest.mark.parametrize("chain,dim,repel", [

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ref_cases as C
+from faml_plan import assert_census, assert_schedule, run_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +121,64 @@ def test_m2_streamed_aggregates(ctx, man, golden, monkeypatch, name, env):
 
 def test_m3_streamed_path(ctx, man, golden):
     got, want = _ml(ctx, man, golden, "M3")
+    assert np.array_equal(got, want)
+
+
+def _ml_plan(ctx, man, golden, monkeypatch, name, env=None):
+    """A case through ge_faml_plan_* under the GE_FAML_RES_CAP its size classes need:
+    (coordinates, the fixture's, the sizes by class, the plan's census and schedule)."""
+    case = C.ml_case(name)
+    assert C.input_hashes(case) == man["cases"][name]["inputs"]
+    knob = C.ML_RES_CAP.get(name)
+    if knob is None:
+        monkeypatch.delenv("GE_FAML_RES_CAP", raising=False)
+    else:
+        monkeypatch.setenv("GE_FAML_RES_CAP", knob)
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    got, cls, sched = run_plan(ctx, case)
+    by_class = assert_census(cls, list(np.diff(case["PT"][0])), case["dim"], knob)
+    return got, golden("ref_" + name)["x"], by_class, cls, sched
+
+
+def test_m4_options_large_resident(ctx, man, golden, monkeypatch):
+    """Every scalar option on fractional weights in faml_resident<3, 256, 4096>."""
+    got, want, by_class, cls, _ = _ml_plan(ctx, man, golden, monkeypatch, "M4_options")
+    assert by_class["large"] == [1031, 700, 257] and cls["blocks_large"] == 3
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("mode", ["sweeps", "row-blocks", "ordered"])
+@pytest.mark.parametrize("name", ["M4_nohubs_unweighted", "M5_weight_edges"])
+def test_m4_m5_streamed(ctx, man, golden, monkeypatch, name, mode):
+    """nohubs with the weights ignored, and one 2^61 edge per aggregate (two members of
+    each outside weight_ok, in different row tiles of the largest), on the streamed
+    aggregates as sweeps, row blocks and ordered pairs."""
+    env = {"sweeps": {"GE_FAML_SYM": "1", "GE_FAML_SYM_CHAIN": "0"},
+           "row-blocks": {"GE_FAML_SYM": "1", "GE_FAML_SYM_CHAIN": "1e9"},
+           "ordered": {"GE_FAML_SYM": "0"}}[mode]
+    got, want, by_class, cls, sched = _ml_plan(ctx, man, golden, monkeypatch, name, env)
+    assert by_class["streamed"] == [2600, 320, 700, 257, 1031, 300] and not by_class["large"]
+    assert_schedule(sched, cls, by_class["streamed"], mode)
+    assert np.array_equal(got, want)
+
+
+def test_m5_coarse_edges_packed(ctx, man, golden, monkeypatch):
+    """coords_A outside the domain, at the origin, shared by two joined aggregates, and
+    r_A = 0, in the packed 64- and 256-member kernels."""
+    got, want, by_class, cls, _ = _ml_plan(ctx, man, golden, monkeypatch, "M5_coarse_edges")
+    assert not by_class["large"] and not by_class["streamed"]
+    assert cls["blocks_small"] >= 2 and cls["blocks_mid"] >= 2
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("name,large", [("M6_d1", [1000, 257]), ("M6_d4", [2048, 257])])
+def test_m6_dims_1_and_4(ctx, man, golden, monkeypatch, name, large):
+    """dim 1, and dim 4 with the large kernel at its capacity (2048 eight-double records),
+    every resident class in one level."""
+    got, want, by_class, cls, _ = _ml_plan(ctx, man, golden, monkeypatch, name)
+    assert by_class["large"] == large and by_class["small"] and by_class["mid"]
+    assert cls["blocks_large"] == len(large) and not by_class["streamed"]
     assert np.array_equal(got, want)
 
 

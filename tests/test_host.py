@@ -18,6 +18,9 @@ def test_library_exports_every_declared_symbol():
     L = ge.lib()
     missing = [s for s in syms if not hasattr(L, s)]
     assert not missing, missing
+    assert "ge_faml_plan_classes" in syms and "ge_faml_plan_schedule" in syms
+    unbound = [s for s in syms if s not in ge._SIGS]  # every entry has a ctypes signature
+    assert not unbound, unbound
     assert b"gfx950" in L.ge_version()
 
 

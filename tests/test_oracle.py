@@ -89,6 +89,25 @@ def test_force_atlas_ml(oracle):
     assert np.array_equal(o1, o8)
 
 
+@pytest.mark.parametrize("name", ["M1", "M3"])
+def test_force_atlas_ml_supplied_init_equals_seeded(oracle, name):
+    """orc_force_atlas_ml_init with the seed's own draws is orc_force_atlas_ml: the
+    supplied-start GPU tests (test_gpu_faml_paths.py) rest on this entry."""
+    import ref_cases as C
+    case = C.ml_case(name)
+    n, dim = len(case["vA"]), case["dim"]
+    seeded = C.run_ml(oracle.force_atlas_ml, case)
+    init = oracle.uniform_stream(case["seed"], n * dim)
+    supplied = oracle.force_atlas_ml(case["A"], case["PT"], case["vA"], case["cA"], case["rA"],
+                                     dim, iterations=case["iterations"], init=init, **case["kw"])
+    assert np.array_equal(supplied, seeded)
+    moved = init.copy()
+    moved[::7] += 0.25  # and the start is really read
+    other = oracle.force_atlas_ml(case["A"], case["PT"], case["vA"], case["cA"], case["rA"],
+                                  dim, iterations=case["iterations"], init=moved, **case["kw"])
+    assert not np.array_equal(other, seeded)
+
+
 @pytest.mark.parametrize("cf", [0.3, 0.125])
 def test_partition(oracle, cf):
     A = G.largest_component(G.rmat(900, 5000, seed=6))
