@@ -489,9 +489,10 @@ int ge_force_atlas_ml(ge_ctx* ctx, int n, const int* ip, const int* ix, const do
   });
 }
 
-int ge_partition(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, double cf,
-                 int printing, int positive, double stall, int matching, int merge_leaves,
-                 ge_hier** out) {
+namespace {
+int partition_entry(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, double cf,
+                    int printing, int positive, double stall, int matching, int merge_leaves,
+                    bool single, int num_parts, ge_hier** out) {
   return guarded([&] {
     GE_REQUIRE(out, "null argument");
     GE_REQUIRE(n > 0, "empty graph");
@@ -499,13 +500,13 @@ int ge_partition(ge_ctx* ctx, int n, const int* ip, const int* ix, const double*
                               "reference, src/partitioner.cpp:1680)");
     ge::check_csr(n, ip, ix, dx);
     *out = nullptr;
-    // with a context: the device path (integer weights, symmetric, ascending rows);
+    // with a context: the device path (symmetric, ascending rows, finite weights);
     // otherwise, or when the input needs it, the host path
     const char* force_host = std::getenv("GE_PARTITION_HOST");
     if (ctx && !(force_host && *force_host && *force_host != '0')) {
       try {
         *out = ge::partition_device(ctx, n, ip, ix, dx, cf, printing != 0, positive != 0, stall,
-                                    matching);
+                                    matching, single, num_parts);
       } catch (const ge::Error& e) {
         // only a device capacity limit (the list pool) falls back: the host path
         // computes the same hierarchy.  Anything else -- a resolve that did not
@@ -520,7 +521,46 @@ int ge_partition(ge_ctx* ctx, int n, const int* ip, const int* ix, const double*
     }
     if (!*out)
       *out = ge::partition_incremental(n, ip, ix, dx, cf, printing != 0, positive != 0, stall,
-                                       matching);
+                                       matching, single, num_parts);
+  });
+}
+}  // namespace
+
+int ge_partition(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, double cf,
+                 int printing, int positive, double stall, int matching, int merge_leaves,
+                 ge_hier** out) {
+  return partition_entry(ctx, n, ip, ix, dx, cf, printing, positive, stall, matching, merge_leaves,
+                         false, 0, out);
+}
+
+int ge_partition_single(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx,
+                        int num_parts, int printing, int positive, double stall, int matching,
+                        int merge_leaves, ge_hier** out) {
+  return partition_entry(ctx, n, ip, ix, dx, 0.0, printing, positive, stall, matching, merge_leaves,
+                         true, num_parts, out);
+}
+
+int ge_hier_info(const ge_hier* h, int* path, int* rounds, long long rebuilt[3]) {
+  return guarded([&] {
+    GE_REQUIRE(h, "null argument");
+    if (path) *path = h->path;
+    if (rounds) *rounds = h->rounds;
+    if (rebuilt)
+      for (int q = 0; q < 3; ++q) rebuilt[q] = h->rebuilt[q];
+  });
+}
+
+int ge_hier_final_graph(const ge_hier* h, ge_csr** adj) {
+  return guarded([&] {
+    GE_REQUIRE(h && adj, "null argument");
+    *adj = new ge_csr(h->final_adj);
+  });
+}
+
+int ge_hier_final_alpha(const ge_hier* h, double* alpha) {
+  return guarded([&] {
+    GE_REQUIRE(h && (alpha || h->final_alpha.empty()), "null argument");
+    std::copy(h->final_alpha.begin(), h->final_alpha.end(), alpha);
   });
 }
 

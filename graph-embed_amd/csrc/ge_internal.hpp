@@ -134,6 +134,13 @@ struct ge_csr {
 struct ge_hier {
   std::vector<int> rows, cols;
   std::vector<std::vector<int>> indptr, indices;
+  // which path built it (GE_PARTITION_PATH_*), its rounds, the lists rebuilt by
+  // the device's wave / block / global kernels, and what the round loop ended
+  // with: the alive vertices' adjacency and alpha by `used` slot
+  int path = GE_PARTITION_PATH_HOST, rounds = 0;
+  long long rebuilt[3] = {0, 0, 0};
+  ge_csr final_adj;
+  std::vector<double> final_alpha;
 };
 
 namespace ge {
@@ -175,12 +182,17 @@ void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const
                      const int* d_vA, const double* d_cA, const double* d_rA,
                      const double* d_init, double* d_x, int dim, int iterations,
                      const ge_fa_params& p);
+// single: the one-level overloads (src/partitioner.cpp:970-1544): no snapshots,
+// one P_T over all n columns, and the loop also stops once M <= num_parts
+// (num_parts <= 0: no target); cf is unused.
 ge_hier* partition_incremental(int n, const int* I, const int* J, const double* Dv, double cf,
-                               bool printing, bool positive, double stall, int matching);
+                               bool printing, bool positive, double stall, int matching,
+                               bool single = false, int num_parts = 0);
 // Device path (ge_partition_dev.hip); nullptr when the input needs the host path
-// (non-integer weights, asymmetric A, rows not strictly ascending).
+// (a weight that is not finite or is -0.0, asymmetric A, rows not strictly ascending).
 ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const double* Dv,
-                          double cf, bool printing, bool positive, double stall, int matching);
+                          double cf, bool printing, bool positive, double stall, int matching,
+                          bool single = false, int num_parts = 0);
 // Coarse rows [a0, a1) of P_T A P_T^T (a0 = 0, a1 = m: the whole matrix) into a
 // host CSR of a1 - a0 rows and m columns.  h_pt_ip: P_T's indptr on the host.
 void ptap_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const double* d_dx,

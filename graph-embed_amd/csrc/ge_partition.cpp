@@ -248,7 +248,8 @@ struct Bitmap {
 }  // namespace
 
 ge_hier* partition_incremental(int n, const int* I, const int* J, const double* Dv, double cf,
-                               bool printing, bool positive, double stall, int matching) {
+                               bool printing, bool positive, double stall, int matching,
+                               bool single, int num_parts) {
   const double inf = std::numeric_limits<double>::infinity();
   const bool prof = std::getenv("GE_PROFILE_PARTITION") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -651,7 +652,7 @@ ge_hier* partition_incremental(int n, const int* I, const int* J, const double* 
     M_prev = M;
     const auto t3 = now();
     t_merge += secs(t2, t3);
-    if (1.0 * M / N <= cf) {
+    if (!single && 1.0 * M / N <= cf) {  // the one-level overloads take no snapshot
       snap();
       basis = alive;
       N = M;
@@ -756,8 +757,32 @@ ge_hier* partition_incremental(int n, const int* I, const int* J, const double* 
     if (prof && std::getenv("GE_PROFILE_ROUNDS"))
       std::fprintf(stderr, "round %d alive %d merges %zu rescans_total %lld\n", rounds, M,
                    merges.size(), rescans);
-  } while (1.0 * M / M_prev < stall);
-  snap();
+  }  // :1838; the one-level overloads also stop at their target (:1525)
+  while (1.0 * M / M_prev < stall && !(single && num_parts > 0 && M <= num_parts));
+  snap();  // one level: no snapshot fired, so this is the P_T over all n columns (:1528-1542)
+  h->path = GE_PARTITION_PATH_HOST;
+  h->rounds = rounds;
+  {
+    // the quotient graph the loop ends with, rows and columns by `used` slot,
+    // columns ascending (the reference's map order)
+    ge_csr& fa = h->final_adj;
+    fa.rows = fa.cols = M;
+    fa.indptr.assign(1, 0);
+    h->final_alpha.resize(M);
+    std::vector<std::pair<int, double>> row;
+    for (int x = 0; x < M; ++x) {
+      const int i = alive[x];
+      h->final_alpha[x] = alpha[i];
+      row.clear();
+      adj[i].for_each([&](int k, double w) { row.emplace_back(slot[k], w); });
+      std::sort(row.begin(), row.end());
+      for (const auto& kw : row) {
+        fa.indices.push_back(kw.first);
+        fa.data.push_back(kw.second);
+      }
+      fa.indptr.push_back((int)fa.indices.size());
+    }
+  }
   if (prof)
     std::fprintf(stderr,
                  "partition: n=%d %d rounds %.3fs: scan %.3fs (%lld rescans) resolve %.3fs "
@@ -781,7 +806,10 @@ ge_hier* partition_incremental(int n, const int* I, const int* J, const double* 
   if (prof)
     std::fprintf(stderr, "marks: init %lld resolve %lld gone-nbrs %lld keep %lld late %lld\n",
                  msrc[0], msrc[1], msrc[2], msrc[3], msrc[4]);
-  if (printing) {  // :1880-1889
+  if (printing && single) {  // :1537-1540
+    std::cout << "modularity: " << Q << std::endl;
+    std::cout << "aggregates: " << M << std::endl;
+  } else if (printing) {  // :1880-1889
     std::cout << "modularity: " << Q << std::endl;
     std::cout << "level 0: " << n << " aggregates" << std::endl;
     for (size_t l = 0; l < h->rows.size(); ++l)

@@ -21,10 +21,14 @@
 //    loop ends).
 //  * contraction (:1756-1779): the round's merges form a matching, so the new
 //    adjacency is the quotient graph with summed weights and
-//    alpha[i'] = alpha[i'] + alpha[j'].  For integer weights every sum is exact
-//    in any order, so lists are rebuilt with hash tables and atomics.  Non-integer
-//    weights keep the host path (ge_partition.cpp), where the += order is the
-//    reference's.
+//    alpha[i'] = alpha[i'] + alpha[j'].  Lists are rebuilt with hash tables and
+//    atomics.  For integer weights every sum is exact in any order (exact mode).
+//    For other real weights (ordered mode) a quotient edge still receives at
+//    most four terms, and the reference's += order groups them by the two
+//    members of whichever of its two groups comes later in `merged`: two
+//    accumulators per hash slot reproduce that grouping bit for bit (rebuild_list).
+//    Only inputs with a weight that is not finite or is -0.0, an asymmetric
+//    matrix or unsorted rows keep the host path (ge_partition.cpp).
 //  * swap-pop of `used`, union-find, snapshots (:1797-1834): O(merges) per round,
 //    sequential and order-dependent -> on the host, mirrored into the device
 //    rank array (rank[v] = pointer[v]) by uploading only the changed slots.
@@ -61,6 +65,13 @@ constexpr int kBigLen = 16384;     // scan: one 256-thread block up to this, the
 constexpr int kWaveNeed = 64;      // rebuild: one wave (128-slot LDS table) up to this
 constexpr int kBlockNeed = 2048;   // rebuild: one block (4096-slot LDS table) up to this
 constexpr int kBlockSlots = 4096;
+// Ordered mode (real weights) keeps two weight accumulators per slot: the block
+// table is half the size (2048 slots: 8 + 2 x 16 KB of LDS), longer lists go to
+// the global table.
+constexpr int kBlockNeedOrd = 1024;
+constexpr int kBlockSlotsOrd = 2048;
+// merge order key of a vertex that kept no merge this round (above every key)
+constexpr unsigned long long kNoKey = ~0ull;
 // Hub lists (longer than kPatchMin) are patched in place after a round instead of
 // rebuilt (patch_list): at most kPatchGone absorbed neighbours and a partner list
 // of at most kPatchGone entries, in LDS sets of kPatchSet slots.
@@ -164,7 +175,12 @@ struct Dev {
   int* t2arg2;
   double* t2w2;
   double* t2b3;
-  int patch;    // 0: every dirty list is rebuilt (GE_PARTITION_NO_PATCH)
+  int patch;    // 0: every dirty list is rebuilt (GE_PARTITION_NO_PATCH, ordered mode)
+  // ordered mode only: position of the keeper's merge in the reference's `merged`
+  // (pass, proposer's `used` slot), kNoKey otherwise; second accumulators of the
+  // global tables
+  unsigned long long* okey;
+  double* gw1;
   int prof;     // GE_PROFILE_PARTITION: count rescans by reason
 };
 
@@ -880,6 +896,7 @@ __device__ void resolve_block(Dev d, int pass, int cidx) {
 }
 
 // ---- contraction (:1756-1779) -----------------------------------------------
+template <bool Ord>
 __global__ void merge_apply_kernel(Dev d, int round) {
   const int count = d.cnt[C_MERGE];
   const int stride = gridDim.x * blockDim.x;
@@ -895,6 +912,7 @@ __global__ void merge_apply_kernel(Dev d, int round) {
       d.alive[m.gone] = 0;
       d.alpha[keep] = d.alpha[keep] + d.alpha[m.gone];  // :1770
       d.partner[keep] = m.gone;
+      if (Ord) d.okey[keep] = ((unsigned long long)(unsigned)m.pass << 32) | (unsigned)m.rank;
       d.kst[keep] = round;
       d.dirty[keep] = 1;
       d.touched[keep] = 0;  // :1830
@@ -945,7 +963,9 @@ __device__ inline unsigned pow2_at_least(unsigned x) {
   return p;
 }
 
+template <bool Ord>
 __global__ void classify_kernel(Dev d) {
+  constexpr int kNeedB = Ord ? kBlockNeedOrd : kBlockNeed;
   const int count = d.cnt[C_DIRTY];
   const int stride = gridDim.x * blockDim.x;
   const int rounds = (count + stride - 1) / stride;
@@ -958,10 +978,10 @@ __global__ void classify_kernel(Dev d) {
       need = d.alen[u] + (g >= 0 ? d.alen[g] : 0);
     }
     const bool w = x < count && need <= kWaveNeed;
-    const bool b = x < count && need > kWaveNeed && need <= kBlockNeed;
+    const bool b = x < count && need > kWaveNeed && need <= kNeedB;
     wave_append(d.lw, &d.cnt[C_W], w, u);
     wave_append(d.lb, &d.cnt[C_B], b, u);
-    if (x < count && need > kBlockNeed) {
+    if (x < count && need > kNeedB) {
       const unsigned slots = pow2_at_least(2u * (unsigned)need);
       const int at = atomicAdd(&d.cnt[C_G], 1);
       d.lg[at] = u;
@@ -984,31 +1004,51 @@ __device__ inline unsigned slot_hash(int k) { return (unsigned)k * 2654435761u; 
 // Rebuild u's list as sum_{members} (rep(k), w), dropping rep(k) == u, into a
 // hash table (LDS or global) of mask+1 slots shared by `nt` threads; then write
 // it back in place (fits) or to fresh pool space.
-template <class Key, class W>
-__device__ void rebuild_list(const Dev& d, int u, Key* tk, W* tw, int mask, int tid, int nt,
-                             int* s_cnt, long long* s_dst) {
+//
+// Ord (real weights): the round's merges form a matching, so a quotient edge
+// (u, r) receives at most four old entries, and the reference's += order
+// (:1756-1779) sums them as S_a + S_b, where a and b are the two members of
+// whichever of the two groups comes later in `merged` and S_x adds the (at most
+// two) entries touching x.  Each S_x goes to its own accumulator (tw, tw1): two
+// terms added to 0.0 in either order give the same bits (no entry is -0.0), and
+// the write-out adds the two accumulators (+ 0.0 changes nothing for the same
+// reason).
+template <bool Ord, class Key, class W>
+__device__ void rebuild_list(const Dev& d, int u, Key* tk, W* tw, W* tw1, int mask, int tid,
+                             int nt, int* s_cnt, long long* s_dst) {
   for (int s = tid; s <= mask; s += nt) {
     tk[s] = -1;
     tw[s] = 0.0;
+    if (Ord) tw1[s] = 0.0;
   }
   if (tid == 0) *s_cnt = 0;
   drain();
   __syncthreads();
   const int g = d.partner[u];
+  unsigned long long ku = kNoKey;
+  if (Ord) ku = d.okey[u];
   for (int m = 0; m < 2; ++m) {
     const int v = m == 0 ? u : g;
     if (v < 0) break;
     const int len = d.alen[v];
     const long long o = d.aoff[v];
     for (int t = tid; t < len; t += nt) {
-      const int r = d.rep[d.akey[o + t]];
+      const int x = d.akey[o + t];
+      const int r = d.rep[x];
       if (r == u) continue;  // the merged pair's own edge: into alpha (:1767-1770)
       const double w = d.aw[o + t];
+      W* acc = tw;
+      if (Ord) {
+        // r's group merges after u's (or not at all): split by r's member, else by u's
+        const unsigned long long kr = d.okey[r];
+        const bool second = (kr == kNoKey || kr > ku) ? x != r : m != 0;
+        if (second) acc = tw1;
+      }
       unsigned h = slot_hash(r) & (unsigned)mask;
       while (true) {
         const int prev = atomicCAS(&tk[h], -1, r);
         if (prev == -1 || prev == r) {
-          atomicAdd(&tw[h], w);  // integer weights: exact in any order
+          atomicAdd(&acc[h], w);  // exact mode: integers, exact in any order
           break;
         }
         h = (h + 1) & (unsigned)mask;
@@ -1056,7 +1096,7 @@ __device__ void rebuild_list(const Dev& d, int u, Key* tk, W* tw, int mask, int 
       if (k >= 0) {
         const int at = base + __popcll(m & ((1ull << lane_id()) - 1ull));
         d.akey[dst + at] = k;
-        d.aw[dst + at] = tab_load(&tw[s]);
+        d.aw[dst + at] = Ord ? tab_load(&tw[s]) + tab_load(&tw1[s]) : tab_load(&tw[s]);
       }
     }
   }
@@ -1242,19 +1282,24 @@ __device__ bool patch_list(const Dev& d, int u, PatchLds& s, int tid, int nt) {
   return true;
 }
 
+template <bool Ord>
 __global__ void __launch_bounds__(64) rebuild_wave_kernel(Dev d) {
   __shared__ int tk[2 * kWaveNeed];
   __shared__ double tw[2 * kWaveNeed];
+  __shared__ double tw1[Ord ? 2 * kWaveNeed : 1];
   __shared__ int s_cnt;
   __shared__ long long s_dst;
   const int count = d.cnt[C_W];
   for (int x = blockIdx.x; x < count; x += gridDim.x)
-    rebuild_list(d, d.lw[x], tk, tw, 2 * kWaveNeed - 1, threadIdx.x, 64, &s_cnt, &s_dst);
+    rebuild_list<Ord>(d, d.lw[x], tk, tw, tw1, 2 * kWaveNeed - 1, threadIdx.x, 64, &s_cnt, &s_dst);
 }
 
+template <bool Ord>
 __global__ void __launch_bounds__(256) rebuild_block_kernel(Dev d) {
-  __shared__ int tk[kBlockSlots];
-  __shared__ double tw[kBlockSlots];
+  constexpr int kSlots = Ord ? kBlockSlotsOrd : kBlockSlots;
+  __shared__ int tk[kSlots];
+  __shared__ double tw[kSlots];
+  __shared__ double tw1[Ord ? kSlots : 1];
   __shared__ int s_cnt;
   __shared__ long long s_dst;
   const int count = d.cnt[C_B];
@@ -1262,8 +1307,8 @@ __global__ void __launch_bounds__(256) rebuild_block_kernel(Dev d) {
     const int u = d.lb[x];
     const int g = d.partner[u];
     const int need = d.alen[u] + (g >= 0 ? d.alen[g] : 0);
-    const int slots = (int)pow2_at_least(2u * (unsigned)need);  // <= kBlockSlots
-    rebuild_list(d, u, tk, tw, slots - 1, threadIdx.x, 256, &s_cnt, &s_dst);
+    const int slots = (int)pow2_at_least(2u * (unsigned)need);  // <= kSlots
+    rebuild_list<Ord>(d, u, tk, tw, tw1, slots - 1, threadIdx.x, 256, &s_cnt, &s_dst);
   }
 }
 
@@ -1277,11 +1322,49 @@ __global__ void __launch_bounds__(1024) rebuild_global_kernel(Dev d) {
     if (threadIdx.x == 0) d.pcnt[d.lg[x]] = 0;  // the bucket cursor, for the next round
     if (patched) continue;
     __syncthreads();
-    rebuild_list(d, d.lg[x], d.gkey + d.gofs[x], d.gw + d.gofs[x], d.gmask[x], threadIdx.x,
-                 (int)blockDim.x, &s_cnt, &s_dst);
+    rebuild_list<false>(d, d.lg[x], d.gkey + d.gofs[x], d.gw + d.gofs[x], (double*)nullptr,
+                        d.gmask[x], threadIdx.x, (int)blockDim.x, &s_cnt, &s_dst);
   }
 }
 
+// ordered mode: no hub patches (they add in place in any order), two accumulators
+__global__ void __launch_bounds__(1024) rebuild_global_ord_kernel(Dev d) {
+  __shared__ int s_cnt;
+  __shared__ long long s_dst;
+  const int count = d.cnt[C_G];
+  for (int x = blockIdx.x; x < count; x += gridDim.x)
+    rebuild_list<true>(d, d.lg[x], d.gkey + d.gofs[x], d.gw + d.gofs[x], d.gw1 + d.gofs[x],
+                       d.gmask[x], threadIdx.x, (int)blockDim.x, &s_cnt, &s_dst);
+}
+
+// The alive lists at loop exit, packed in `used` order (ge_hier_final_graph):
+// lens first (okey/ow null), then the entries at the offsets the host summed.
+__global__ void export_lists_kernel(Dev d, int M, const int* __restrict__ used,
+                                    const long long* __restrict__ off, int* __restrict__ olen,
+                                    int* __restrict__ okeys, double* __restrict__ ow,
+                                    double* __restrict__ oalpha) {
+  const int lane = lane_id();
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nw = (gridDim.x * blockDim.x) >> 6;
+  for (int x = wave; x < M; x += nw) {
+    const int u = used[x];
+    const int len = d.alen[u];
+    if (!okeys) {
+      if (lane == 0) {
+        olen[x] = len;
+        oalpha[x] = d.alpha[u];
+      }
+      continue;
+    }
+    const long long o = d.aoff[u], q = off[x];
+    for (int t = lane; t < len; t += 64) {
+      okeys[q + t] = d.akey[o + t];
+      ow[q + t] = d.aw[o + t];
+    }
+  }
+}
+
+template <bool Ord>
 __global__ void dirty_reset_kernel(Dev d, int round) {
   const int count = d.cnt[C_DIRTY];
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the next contraction
@@ -1292,6 +1375,7 @@ __global__ void dirty_reset_kernel(Dev d, int round) {
     const int u = d.dlist[x];
     d.dirty[u] = 0;
     d.partner[u] = -1;
+    if (Ord) d.okey[u] = kNoKey;
     d.chg[u] = round;
   }
 }
@@ -1318,9 +1402,11 @@ __global__ void rank_update_kernel(Dev d, int count, const int2* __restrict__ ch
 
 
 // ---- set-up ------------------------------------------------------------------
-// Eligibility (rows strictly ascending -> no duplicate keys; integer weights;
-// A symmetric with equal weights) and the lists: row i minus its diagonal
-// entry (:1569-1571).  One wave per row.
+// Eligibility (C_BAD bit 0: rows not strictly ascending -> duplicate keys, a
+// weight that is not finite or is -0.0, A not symmetric with equal weights; bit
+// 1: a weight that is not an integer of at most 2^40 -> ordered mode) and the
+// lists: row i minus its diagonal entry (:1569-1571).  One wave per row.  The
+// row sums computed here serve the exact mode only.
 __global__ void init_lists_kernel(int n, const int* __restrict__ ip, const int* __restrict__ ix,
                                   const double* __restrict__ dx, Dev d, double* __restrict__ rowsum,
                                   double* __restrict__ abs_total, double* __restrict__ self_total) {
@@ -1330,13 +1416,15 @@ __global__ void init_lists_kernel(int n, const int* __restrict__ ip, const int* 
   for (int i = wave; i < n; i += nw) {
     const int b = ip[i], e = ip[i + 1];
     int self = -1;
-    bool bad = false;
+    bool bad = false, real = false;
     double s = 0.0, sa = 0.0, sd = 0.0;
     for (int t = b + lane; t < e; t += 64) {
       const int j = ix[t];
       const double w = dx[t];
       if (j < 0 || j >= n || (t + 1 < e && !(j < ix[t + 1]))) bad = true;
-      if (!(w == trunc(w)) || !(fabs(w) <= 1099511627776.0)) bad = true;  // |w| <= 2^40
+      // not finite, or -0.0 (the reference's map[k] += starts from +0.0): host path
+      if (!(fabs(w) <= 1.7976931348623157e308) || (w == 0.0 && signbit(w))) bad = true;
+      if (!(w == trunc(w)) || !(fabs(w) <= 1099511627776.0)) real = true;  // |w| <= 2^40
       if (j == i) {
         self = t;
         sd += w;
@@ -1361,6 +1449,9 @@ __global__ void init_lists_kernel(int n, const int* __restrict__ ip, const int* 
     }
     if (__ballot(bad)) {
       if (lane == 0) atomicOr(&d.cnt[C_BAD], 1);
+    }
+    if (__ballot(real)) {  // eligible for the ordered mode only
+      if (lane == 0) atomicOr(&d.cnt[C_BAD], 2);
     }
     const unsigned long long sm = __ballot(self >= 0);
     const int sp = sm ? __shfl(self, __ffsll((long long)sm) - 1) : -1;
@@ -1435,11 +1526,13 @@ inline unsigned blocks_for(long long n, int t) { return (unsigned)std::max<long 
 
 }  // namespace
 
-// Device path of partition::partition.  Returns nullptr (nothing computed) when
-// the input needs the host path: non-integer or too large weights, an
-// asymmetric matrix, or rows that are not strictly ascending.
+// Device path of partition::partition and of its one-level overloads (single).
+// Returns nullptr (nothing computed) when the input needs the host path: a weight
+// that is not finite or is -0.0, an asymmetric matrix, or rows that are not
+// strictly ascending.
 ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const double* Dv,
-                          double cf, bool printing, bool positive, double stall, int matching) {
+                          double cf, bool printing, bool positive, double stall, int matching,
+                          bool single, int num_parts) {
   DeviceGuard guard(ctx);
   hipStream_t st = ctx->stream;
   const bool prof = std::getenv("GE_PROFILE_PARTITION") != nullptr;
@@ -1553,13 +1646,16 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
   GE_HIP(hipMemcpyAsync(h_sums, sums.p, sizeof(h_sums), hipMemcpyDeviceToHost, st));
   GE_HIP(hipStreamSynchronize(st));
   note("lists built");
-  if (bad || !(h_sums[0] < 4503599627370496.0)) {  // sum |w| < 2^52
+  if (bad & 1) {
     if (progress)
-      std::fprintf(stderr, "partition_device: input needs the host path (%s)\n",
-                   bad ? "non-integer weights, asymmetric or unsorted rows"
-                       : "weights sum to 2^52 or more");
+      std::fprintf(stderr, "partition_device: input needs the host path (a weight that is not "
+                           "finite or is -0.0, an asymmetric matrix or unsorted rows)\n");
     return nullptr;
   }
+  // exact mode: integer weights, |w| <= 2^40, sum |w| < 2^52; otherwise ordered
+  const bool ordered = (bad & 2) || !(h_sums[0] < 4503599627370496.0);
+  if (progress && ordered)
+    std::fprintf(stderr, "partition_device: real weights, ordered contraction\n");
   {
     bool pos = true;
     for (long long e = 0; e < nnz && pos; ++e) pos = Dv[e] > 0.0;
@@ -1568,13 +1664,37 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
   d_ix.release();
   d_dx.release();
   d_ip.release();
-  // T = sum of all entries (:1580-1591): exact (integers), any order
   std::vector<double> h_rowsum(n);
-  rowsum.download(h_rowsum.data(), n, st);
-  GE_HIP(hipStreamSynchronize(st));
-  double T = 0.0;
-  for (int i = 0; i < n; ++i) T += h_rowsum[i];
-  const double d_sum = h_sums[1];
+  double T = 0.0, d_sum = 0.0;
+  DevBuf<unsigned long long> okey;
+  DevBuf<double> gw1;
+  if (ordered) {
+    // the reference's sums in its order (:1563-1591): rows serially in CSR order,
+    // T over all entries in storage order (not the sum of the row sums)
+    for (int i = 0; i < n; ++i) {
+      double s = 0.0;
+      for (int e = I[i]; e < I[i + 1]; ++e) {
+        s += Dv[e];
+        if (J[e] == i) d_sum += Dv[e];
+        T += Dv[e];
+      }
+      h_rowsum[i] = s;
+    }
+    rowsum.upload(h_rowsum.data(), n, st);
+    okey.alloc(n);
+    gw1.alloc(gcap);
+    GE_HIP(hipMemsetAsync(okey.p, 0xFF, sizeof(unsigned long long) * n, st));  // kNoKey
+    d.okey = okey.p;
+    d.gw1 = gw1.p;
+    d.patch = 0;  // hub patches add in place in any order: every dirty list is rebuilt
+    GE_HIP(hipStreamSynchronize(st));  // (h_rowsum is pageable)
+  } else {
+    // T = sum of all entries (:1580-1591): exact (integers), any order
+    rowsum.download(h_rowsum.data(), n, st);
+    GE_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) T += h_rowsum[i];
+    d_sum = h_sums[1];
+  }
   d.T = T;
   hipLaunchKernelGGL(init_state_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, d, rowsum.p);
   unsigned long long top0 = (unsigned long long)nnz;
@@ -1743,6 +1863,7 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     }
     if (rounds <= 2) note("round: matching passes done");
     rb.merges = h_cnt[C_MERGE];
+    for (int q = 0; q < 3; ++q) h->rebuilt[q] += h_cnt[C_SH_W + q];  // the previous contraction
     if (prof) {
       for (int q = 0; q < 4; ++q) {  // previous round's contraction (DIRTY W B G)
         stat[C_DIRTY + q] += h_cnt[C_SH_DIRTY + q];
@@ -1793,14 +1914,24 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
       }
       // contraction on the device (asynchronous) while the host does the
       // order-dependent bookkeeping
-      hipLaunchKernelGGL(merge_apply_kernel, dim3(blocks_for(nm, 256)), dim3(256), 0, st, d, rounds);
-      hipLaunchKernelGGL(mark_dirty_kernel, dim3(blocks_for(nm, 4)), dim3(256), 0, st, d);
-      hipLaunchKernelGGL(classify_kernel, dim3(1024), dim3(256), 0, st, d);
-      hipLaunchKernelGGL(pair_scatter_kernel, dim3(1024), dim3(256), 0, st, d);
-      hipLaunchKernelGGL(rebuild_wave_kernel, dim3(8192), dim3(64), 0, st, d);
-      hipLaunchKernelGGL(rebuild_block_kernel, dim3(1024), dim3(256), 0, st, d);
-      hipLaunchKernelGGL(rebuild_global_kernel, dim3(256), dim3(1024), 0, st, d);
-      hipLaunchKernelGGL(dirty_reset_kernel, dim3(1024), dim3(256), 0, st, d, rounds);
+      if (!ordered) {
+        hipLaunchKernelGGL(merge_apply_kernel<false>, dim3(blocks_for(nm, 256)), dim3(256), 0, st, d, rounds);
+        hipLaunchKernelGGL(mark_dirty_kernel, dim3(blocks_for(nm, 4)), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(classify_kernel<false>, dim3(1024), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(pair_scatter_kernel, dim3(1024), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(rebuild_wave_kernel<false>, dim3(8192), dim3(64), 0, st, d);
+        hipLaunchKernelGGL(rebuild_block_kernel<false>, dim3(1024), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(rebuild_global_kernel, dim3(256), dim3(1024), 0, st, d);
+        hipLaunchKernelGGL(dirty_reset_kernel<false>, dim3(1024), dim3(256), 0, st, d, rounds);
+      } else {  // real weights: the reference's += order (rebuild_list<true>), no patches
+        hipLaunchKernelGGL(merge_apply_kernel<true>, dim3(blocks_for(nm, 256)), dim3(256), 0, st, d, rounds);
+        hipLaunchKernelGGL(mark_dirty_kernel, dim3(blocks_for(nm, 4)), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(classify_kernel<true>, dim3(1024), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(rebuild_wave_kernel<true>, dim3(8192), dim3(64), 0, st, d);
+        hipLaunchKernelGGL(rebuild_block_kernel<true>, dim3(1024), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(rebuild_global_ord_kernel, dim3(256), dim3(1024), 0, st, d);
+        hipLaunchKernelGGL(dirty_reset_kernel<true>, dim3(1024), dim3(256), 0, st, d, rounds);
+      }
       GE_HIP(hipGetLastError());
       if (rounds <= 2 && progress) {  // profiling the first rounds: wait for the contraction
         GE_HIP(hipStreamSynchronize(st));
@@ -1809,7 +1940,8 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     }
     M_prev = M;
     M -= nm;  // the swap-pop below removes nm entries of `used`
-    const bool more = 1.0 * M / M_prev < stall;  // :1838
+    // :1838; the one-level overloads also stop at their target (:1525)
+    const bool more = 1.0 * M / M_prev < stall && !(single && num_parts > 0 && M <= num_parts);
     if (more) {
       if (alist_len > M + M / 4 + 1024) {  // drop the dead entries of the alive list
         GE_HIP(hipMemsetAsync(cnt.p + C_ALIVE2, 0, sizeof(int), st));
@@ -1833,7 +1965,7 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     double dQ = 0.0;
     for (const auto& m : order) dQ += m.eta;  // :1749
     Q += dQ;                                  // :1784
-    if (1.0 * M_prev / N <= cf) {  // :1797-1815 (before this round's swap-pop)
+    if (!single && 1.0 * M_prev / N <= cf) {  // :1797-1815 (before this round's swap-pop)
       const int M_now = M;
       M = M_prev;  // snap() reads the pre-round count
       snap();
@@ -1880,8 +2012,67 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
                    rstat[C_PF_FIT]);
     if (!more) break;
   } while (true);
-  GE_HIP(hipStreamSynchronize(st));
-  snap();  // :1840-1852
+  {
+    // the last contraction's list counts (no scan followed to move them) and the
+    // hub lists patched instead of rebuilt
+    int last[NCNT];
+    GE_HIP(hipMemcpyAsync(last, cnt.p, sizeof(last), hipMemcpyDeviceToHost, st));
+    GE_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < 3; ++q) h->rebuilt[q] += last[C_W + q];
+    h->rebuilt[2] -= last[C_PATCH];
+  }
+  h->path = ordered ? GE_PARTITION_PATH_DEVICE_ORDERED : GE_PARTITION_PATH_DEVICE_EXACT;
+  h->rounds = rounds;
+  {
+    // the quotient graph the loop ends with: the alive lists in `used` order, keys
+    // renamed to `used` slots and sorted ascending (the reference's map order)
+    DevBuf<int> d_used(M), d_len(M);
+    DevBuf<double> d_al(M);
+    d_used.upload(used.data(), M, st);
+    const unsigned eb = blocks_for((long long)M * 64, 256);
+    hipLaunchKernelGGL(export_lists_kernel, dim3(std::min(eb, 4096u)), dim3(256), 0, st, d, M,
+                       d_used.p, (const long long*)nullptr, d_len.p, (int*)nullptr,
+                       (double*)nullptr, d_al.p);
+    GE_HIP(hipGetLastError());
+    std::vector<int> len(M);
+    h->final_alpha.resize(M);
+    d_len.download(len.data(), M, st);
+    d_al.download(h->final_alpha.data(), M, st);
+    GE_HIP(hipStreamSynchronize(st));
+    std::vector<long long> off(M + 1, 0);
+    for (int x = 0; x < M; ++x) off[x + 1] = off[x] + len[x];
+    const long long fz = off[M];
+    GE_REQUIRE(fz <= 0x7FFFFFFFLL, "partition_device: the final graph exceeds int offsets");
+    DevBuf<long long> d_off(M + 1);
+    DevBuf<int> d_k(std::max<long long>(fz, 1));
+    DevBuf<double> d_w(std::max<long long>(fz, 1));
+    d_off.upload(off.data(), M + 1, st);
+    hipLaunchKernelGGL(export_lists_kernel, dim3(std::min(eb, 4096u)), dim3(256), 0, st, d, M,
+                       d_used.p, d_off.p, d_len.p, d_k.p, d_w.p, d_al.p);
+    GE_HIP(hipGetLastError());
+    std::vector<int> fk(fz);
+    std::vector<double> fw(fz);
+    d_k.download(fk.data(), fz, st);
+    d_w.download(fw.data(), fz, st);
+    GE_HIP(hipStreamSynchronize(st));
+    ge_csr& fa = h->final_adj;
+    fa.rows = fa.cols = M;
+    fa.indptr.assign(off.begin(), off.end());
+    fa.indices.resize(fz);
+    fa.data.resize(fz);
+    std::vector<std::pair<int, double>> row;
+    for (int x = 0; x < M; ++x) {
+      row.clear();
+      for (long long e = off[x]; e < off[x + 1]; ++e) row.emplace_back(pointer[fk[e]], fw[e]);
+      std::sort(row.begin(), row.end());
+      for (long long e = off[x]; e < off[x + 1]; ++e) {
+        fa.indices[e] = row[e - off[x]].first;
+        fa.data[e] = row[e - off[x]].second;
+      }
+    }
+  }
+  // :1840-1852; one level: no snapshot fired, so this is the P_T over all n columns (:1528-1542)
+  snap();
   if (prof)
     std::fprintf(stderr,
                  "partition_device: n=%d nnz=%lld %d rounds %lld merges %.3fs (device rounds "
@@ -1902,7 +2093,10 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
                  "partition_device rescans of lists > %d entries by reason: changed %d, bound "
                  "failed %d, argmax touched %d\n",
                  kSmallLen, h_cnt[C_R_CHG], h_cnt[C_R_BOUND], h_cnt[C_R_PASS]);
-  if (printing) {  // :1880-1889
+  if (printing && single) {  // :1537-1540
+    std::cout << "modularity: " << Q << std::endl;
+    std::cout << "aggregates: " << M << std::endl;
+  } else if (printing) {  // :1880-1889
     std::cout << "modularity: " << Q << std::endl;
     std::cout << "level 0: " << n << " aggregates" << std::endl;
     for (size_t l = 0; l < h->rows.size(); ++l)

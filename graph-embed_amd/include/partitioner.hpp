@@ -4,10 +4,12 @@
 //   partition(A, coarseningFactor, ...)       src/partitioner.cpp:1550-1893 (hierarchy)
 // plus the extension galerkin(P_T, A) = P_T A P_T^T on the device (what the
 // drivers compute with linalgcpp at examples/embed.cpp:96-98).
-// The sibling overloads partition(A, bool...) / partition(A, int numParts, ...)
-// and the float variants partitionTest/Base/Base2 stay declared, so overload
-// resolution is the reference's (a double selects the hierarchy, an int
-// numParts), but they are outside this library's scope and throw.
+//   partition(A, printing, ...)               src/partitioner.cpp:970-1266 (one P_T)
+//   partition(A, numParts, printing, ...)     src/partitioner.cpp:1272-1544 (one P_T)
+// Overload resolution is the reference's (a double selects the hierarchy, an int
+// numParts, a bool or nothing the single P_T).  The float variants
+// partitionTest/Base/Base2 stay declared but are outside this library's scope
+// and throw.
 #ifndef PARTITIONER_HPP
 #define PARTITIONER_HPP
 
@@ -57,14 +59,38 @@ inline SparseMatrix partitionBase(const SparseMatrix&, const float = 1.0) {
 inline SparseMatrix partitionBase2(const SparseMatrix&, const float = 1.0) {
   out_of_scope("partitionBase2");
 }
-inline SparseMatrix partition(const SparseMatrix&, const bool = false, const bool = true,
-                              const double = 1.0, const int = 2, const bool = false) {
-  out_of_scope("single-level partition(A, printing, ...)");
+namespace detail {
+// num_parts <= 0: no target (the overload without numParts)
+inline SparseMatrix partition_single(const SparseMatrix& A, int num_parts, bool printing,
+                                     bool positiveMerging, double stallStopThreshold,
+                                     int matchingIterations, bool mergeLeaves) {
+  ge_hier* h = nullptr;
+  check(ge_partition_single(context(), A.Rows(), A.GetIndptr().data(), A.GetIndices().data(),
+                            A.GetData().data(), num_parts, printing, positiveMerging,
+                            stallStopThreshold, matchingIterations, mergeLeaves, &h));
+  int rows = 0, cols = 0;
+  check(ge_hier_shape(h, 0, &rows, &cols));
+  std::vector<int> I(rows + 1), J(cols);
+  check(ge_hier_copy(h, 0, I.data(), J.data()));
+  ge_hier_free(h);
+  return SparseMatrix(I, J, std::vector<double>(cols, 1.0), rows, cols);
 }
-inline SparseMatrix partition(const SparseMatrix&, const int, const bool = false,
-                              const bool = true, const double = 1.0, const int = 2,
-                              const bool = false) {
-  out_of_scope("partition(A, numParts, ...)");
+}  // namespace detail
+
+inline SparseMatrix partition(const SparseMatrix& A, const bool printing = false,
+                              const bool positiveMerging = true,
+                              const double stallStopThreshold = 1.0,
+                              const int matchingIterations = 2, const bool mergeLeaves = false) {
+  return detail::partition_single(A, 0, printing, positiveMerging, stallStopThreshold,
+                                  matchingIterations, mergeLeaves);
+}
+inline SparseMatrix partition(const SparseMatrix& A, const int numParts,
+                              const bool printing = false, const bool positiveMerging = true,
+                              const double stallStopThreshold = 1.0,
+                              const int matchingIterations = 2, const bool mergeLeaves = false) {
+  // the reference's loop test is M > numParts: a target <= 0 never stops it
+  return detail::partition_single(A, numParts > 0 ? numParts : 0, printing, positiveMerging,
+                                  stallStopThreshold, matchingIterations, mergeLeaves);
 }
 
 inline std::vector<SparseMatrix> partition(const SparseMatrix& A, const double coarseningFactor,

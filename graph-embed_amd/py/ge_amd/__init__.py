@@ -73,6 +73,12 @@ _SIGS = {
     "ge_partition": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_double,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                     ctypes.c_int, ctypes.POINTER(_vp)]),
+    "ge_partition_single": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "ge_hier_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_hier_final_graph": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "ge_hier_final_alpha": (ctypes.c_int, [_vp, _f64p]),
     "ge_hier_levels": (ctypes.c_int, [_vp, _ip]),
     "ge_hier_shape": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
     "ge_hier_copy": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p]),
@@ -256,6 +262,9 @@ class Context:
     # -- partition (device path) ---------------------------------------------
     def partition(self, A, coarsening_factor, **kw):
         return partition(A, coarsening_factor, ctx=self, **kw)
+
+    def partition_single(self, A, num_parts=None, **kw):
+        return partition_single(A, num_parts, ctx=self, **kw)
 
     # -- ForceAtlas ----------------------------------------------------------
     def force_atlas(self, A, dim, coords=None, iterations=100000, **kw):
@@ -684,17 +693,10 @@ def _take_csr(h):
 
 # -- host-resident entry points (no device needed) ----------------------------
 
-def partition(A, coarsening_factor, printing=False, positive_merging=True, stall=1.0,
-              matching_iterations=2, merge_leaves=False, ctx=None):
-    """Hierarchy of P_T matrices as (indptr, indices, rows, cols) tuples.  With a
-    Context the hierarchy is built on its device (integer weights, symmetric A);
-    without one, or for other inputs, by the library's host path."""
-    ip, ix, dx = _csr(A)
-    h = _vp()
-    _check(lib().ge_partition(ctx.h if ctx is not None else None, len(ip) - 1, ip, ix, dx,
-                              coarsening_factor, int(printing),
-                              int(positive_merging), stall, matching_iterations,
-                              int(merge_leaves), ctypes.byref(h)))
+PATH_HOST, PATH_DEVICE_EXACT, PATH_DEVICE_ORDERED = 0, 1, 2  # GE_PARTITION_PATH_*
+
+
+def _take_hier(h, info):
     try:
         lv = ctypes.c_int()
         _check(lib().ge_hier_levels(h, ctypes.byref(lv)))
@@ -706,9 +708,54 @@ def partition(A, coarsening_factor, printing=False, positive_merging=True, stall
             pix = np.empty(c.value, dtype=np.int32)
             _check(lib().ge_hier_copy(h, l, pip, pix))
             out.append((pip, pix, r.value, c.value))
-        return out
+        if not info:
+            return out
+        path, rounds = ctypes.c_int(), ctypes.c_int()
+        rebuilt = (ctypes.c_longlong * 3)()
+        _check(lib().ge_hier_info(h, ctypes.byref(path), ctypes.byref(rounds), rebuilt))
+        g = _vp()
+        _check(lib().ge_hier_final_graph(h, ctypes.byref(g)))
+        final_graph = _take_csr(g)
+        alpha = np.empty(len(final_graph[0]) - 1, dtype=np.float64)
+        _check(lib().ge_hier_final_alpha(h, alpha))
+        return out, {"path": path.value, "rounds": rounds.value, "rebuilt": list(rebuilt),
+                     "final_graph": final_graph, "final_alpha": alpha}
     finally:
         lib().ge_hier_free(h)
+
+
+def partition(A, coarsening_factor, printing=False, positive_merging=True, stall=1.0,
+              matching_iterations=2, merge_leaves=False, ctx=None, info=False):
+    """Hierarchy of P_T matrices as (indptr, indices, rows, cols) tuples.  With a
+    Context the hierarchy is built on its device (symmetric A with finite weights:
+    integers by the exact contraction, other reals by the ordered one); without
+    one, or for other inputs, by the library's host path.  info=True returns
+    (hierarchy, dict): path (PATH_*), rounds, rebuilt (lists rebuilt by the
+    device's wave / block / global kernels) and the quotient graph the round loop
+    ended with, final_graph (CSR by the last P_T's row numbers) and final_alpha."""
+    ip, ix, dx = _csr(A)
+    h = _vp()
+    _check(lib().ge_partition(ctx.h if ctx is not None else None, len(ip) - 1, ip, ix, dx,
+                              coarsening_factor, int(printing),
+                              int(positive_merging), stall, matching_iterations,
+                              int(merge_leaves), ctypes.byref(h)))
+    return _take_hier(h, info)
+
+
+def partition_single(A, num_parts=None, printing=False, positive_merging=True, stall=1.0,
+                     matching_iterations=2, merge_leaves=False, ctx=None, info=False):
+    """One P_T as (indptr, indices, rows, cols): partition::partition(A, printing,
+    ...) for num_parts=None, partition(A, numParts, ...) otherwise (the rounds
+    also stop once at most num_parts aggregates are left).  Paths and info as in
+    partition()."""
+    ip, ix, dx = _csr(A)
+    h = _vp()
+    _check(lib().ge_partition_single(ctx.h if ctx is not None else None, len(ip) - 1, ip, ix, dx,
+                                     0 if num_parts is None else int(num_parts), int(printing),
+                                     int(positive_merging), stall, matching_iterations,
+                                     int(merge_leaves), ctypes.byref(h)))
+    res = _take_hier(h, info)
+    return (res[0][0], res[1]) if info else res[0]
 
 
 def interpolation_matrix(num_cols, sets):

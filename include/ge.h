@@ -183,13 +183,39 @@ int ge_faml_plan_destroy(ge_faml_plan* plan);
  * mergeLeaves) (include/partitioner.hpp:52-53, src/partitioner.cpp:1550-1893).
  * A must be symmetric.  Level l of the result is P_T[l] (rows x cols, one 1.0
  * per column).  ctx != NULL builds the hierarchy on the context's device
- * (graph-embed_amd/csrc/ge_partition_dev.hip) when A has integer weights and
- * strictly ascending rows; ctx == NULL, other inputs, or GE_PARTITION_HOST=1 take
- * the host path.  Both give the reference's P_T arrays. */
+ * (graph-embed_amd/csrc/ge_partition_dev.hip) when A is symmetric with equal
+ * mirror weights, strictly ascending rows and finite weights none of which is
+ * -0.0: integer weights (|w| <= 2^40, sum |w| < 2^52) by the exact contraction,
+ * any other real weights by the ordered contraction, which adds in the
+ * reference's order.  ctx == NULL, other inputs, or GE_PARTITION_HOST=1 take the
+ * host path.  All give the reference's P_T arrays and its final weights, bit
+ * for bit.  merge_leaves != 0 is rejected. */
 int ge_partition(ge_ctx* ctx, int n, const int* indptr, const int* indices,
                  const double* data, double coarsening_factor, int printing,
                  int positive_merging, double stall_stop_threshold,
                  int matching_iterations, int merge_leaves, ge_hier** out);
+/* Replaces the one-level overloads SparseMatrix partition::partition(A, printing,
+ * ...) (src/partitioner.cpp:970-1266; num_parts <= 0) and partition(A, numParts,
+ * printing, ...) (:1272-1544): the same rounds without snapshots, stopped by the
+ * stall test or once at most num_parts aggregates are left.  The result has
+ * exactly one level, P_T over all n columns.  Same paths as ge_partition. */
+int ge_partition_single(ge_ctx* ctx, int n, const int* indptr, const int* indices,
+                        const double* data, int num_parts, int printing,
+                        int positive_merging, double stall_stop_threshold,
+                        int matching_iterations, int merge_leaves, ge_hier** out);
+/* Which path built h, its rounds, and the lists rebuilt over all rounds by the
+ * device's wave, block and global kernels (zero on the host path).  Any output
+ * pointer may be NULL. */
+#define GE_PARTITION_PATH_HOST 0
+#define GE_PARTITION_PATH_DEVICE_EXACT 1
+#define GE_PARTITION_PATH_DEVICE_ORDERED 2
+int ge_hier_info(const ge_hier* h, int* path, int* rounds, long long rebuilt[3]);
+/* What the round loop ended with: the adjacency a[i][k] of the vertices alive at
+ * loop exit (rows and columns numbered by `used` slot = the last P_T's row
+ * number, columns ascending; free with ge_csr_free) and their alpha (one per row
+ * of the last P_T). */
+int ge_hier_final_graph(const ge_hier* h, ge_csr** adj);
+int ge_hier_final_alpha(const ge_hier* h, double* alpha);
 int ge_hier_levels(const ge_hier* h, int* levels);
 int ge_hier_shape(const ge_hier* h, int level, int* rows, int* cols);
 /* indptr: rows+1 ints, indices: cols ints */
