@@ -221,6 +221,14 @@ void faml_host_dist(ge_comm* comm, int n, const int* ip, const int* ix, const do
                     const int* pip, const int* pix, const int* vA, const double* cA,
                     const double* rA, double* X, int dim, int iterations,
                     const ge_fa_params& p);
+// embedViaMinimization (ge_minimize.cpp) and one level of anyToMultilevel over it
+// for the aggregates aggs[0..naggs) (nullptr: all), on the host; local_of[g] is
+// g's position in its aggregate's member list.
+void embed_via_minimization(int n, const int* I, const int* J, int dim, double* X,
+                            bool init_random, unsigned seed, int iterations);
+void minimize_ml_host(const int* I, const int* J, const int* PI, const int* PJ, const int* vA,
+                      const int* local_of, const double* cA, const double* rA, int dim,
+                      int iterations, double* coords, const int* aggs, int naggs);
 // the embed orchestration (src/embed.cpp:561-796); comm == nullptr: one GPU
 void embed_impl(ge_ctx* ctx, ge_comm* comm, int levels, const int* a_n, const int* a_off,
                 const int* a_nz_off, const int* a_ip, const int* a_ix, const double* a_dx,

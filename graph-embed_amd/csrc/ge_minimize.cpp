@@ -5,12 +5,17 @@
 // unit directions on the energy sum_r 1/|x_i - x_r| + w sum_(i,r) |x_i - x_r|^2,
 // w = 1e6, then a move to the direction of least energy.
 //
-// Host C++.  It is off the embed() path, and its work per vertex is a chain of
-// serial n-term sums whose order fixes the bits (the line search branches on
-// their signs), so the device has no lane parallelism to offer inside one call;
-// the 2d directions of a vertex are independent and run on OpenMP threads.
+// Host C++.  Inside one call the work per vertex is a chain of serial n-term
+// sums whose order fixes the bits (the line search branches on their signs), so a
+// single call stays on the host; the 2d directions of a vertex are independent and
+// run on OpenMP threads.  A level of anyToMultilevel(embedViaMinimization) is a
+// different matter: its aggregates are independent, and ge_minimize_dev.hip runs
+// them as one batched device call.  minimize_ml_host below is that level's host
+// twin (ctx == NULL, GE_MINIMIZE_HOST=1, inputs the device path does not take, and
+// the aggregates beyond the device's LDS capacity).
 // Every sum keeps the reference's order and operand grouping (-ffp-contract=off).
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -153,6 +158,54 @@ void embed_via_minimization(int n, const int* I, const int* J, int dim, double* 
     for (int i = 0; i < n; ++i)
       for (int k = 0; k < dim; ++k) X[(size_t)i * dim + k] = X[(size_t)i * dim + k] / max_length;
   }
+}
+
+// anyToMultilevel(embedViaMinimization) (src/embed.cpp:23-83) for the aggregates
+// aggs[0..naggs) (aggs == nullptr: all m).  Per aggregate a: the members' internal
+// edges as an r x r pattern (columns sorted, duplicates merged, as the reference's
+// CooMatrix::ToSparse leaves them), `iterations` sweeps from a zero start, the
+// result normalised by its largest norm and placed in a's ball.  local_of[g]: g's
+// position in its aggregate's member list.
+void minimize_ml_host(const int* I, const int* J, const int* PI, const int* PJ, const int* vA,
+                      const int* local_of, const double* cA, const double* rA, int dim,
+                      int iterations, double* coords, const int* aggs, int naggs) {
+  auto one = [&](int a) {
+    const int* v = PJ + PI[a];
+    const int r = PI[a + 1] - PI[a];
+    std::vector<int> ci(r + 1, 0), cj, cols;
+    for (int i = 0; i < r; ++i) {
+      cols.clear();
+      for (int kk = I[v[i]]; kk < I[v[i] + 1]; ++kk)
+        if (vA[J[kk]] == a) cols.push_back(local_of[J[kk]]);
+      std::sort(cols.begin(), cols.end());
+      cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+      cj.insert(cj.end(), cols.begin(), cols.end());
+      ci[i + 1] = (int)cj.size();
+    }
+    std::vector<double> X((size_t)r * dim, 0.0);
+    embed_via_minimization(r, ci.data(), cj.data(), dim, X.data(), false, 0, iterations);
+    double mx = 0.0;
+    for (int i = 0; i < r; ++i) {
+      double acc = 0.0;  // magnitude (include/forceatlas.hpp:80-87)
+      for (int k = 0; k < dim; ++k) acc += X[(size_t)i * dim + k] * X[(size_t)i * dim + k];
+      const double mg = std::sqrt(acc);
+      if (mg > mx) mx = mg;
+    }
+    for (int i = 0; i < r; ++i)
+      for (int k = 0; k < dim; ++k)
+        coords[(size_t)v[i] * dim + k] =
+            cA[(size_t)a * dim + k] + rA[a] * (X[(size_t)i * dim + k] / mx);
+  };
+  // aggregates are independent: the small ones (whose calls are serial inside) run
+  // on OpenMP threads, the others one after another with their directions on threads
+  std::vector<int> small, large;
+  for (int q = 0; q < naggs; ++q) {
+    const int a = aggs ? aggs[q] : q;
+    (PI[a + 1] - PI[a] > 64 ? large : small).push_back(a);
+  }
+  for (int a : large) one(a);
+#pragma omp parallel for schedule(dynamic, 1)
+  for (size_t q = 0; q < small.size(); ++q) one(small[q]);
 }
 
 }  // namespace ge

@@ -6,7 +6,8 @@
 // forceAtlasMultilevel per level) so its r_A / coords_A out-parameters are
 // available.  Both print the reference's "embedding layer" lines.
 // The alternative embedders (embedViaMinimization, anyToMultilevel, embedVia,
-// embedViaMultilevel, src/embed.cpp:23-559) are implemented at the end.
+// embedViaMultilevel, src/embed.cpp:23-559) are implemented at the end, with
+// minimizationToMultilevel: anyToMultilevel(embedViaMinimization) as one device call.
 #ifndef EMBED_HPP
 #define EMBED_HPP
 
@@ -186,6 +187,27 @@ inline MultilevelEmbedder anyToMultilevel(
       for (int i = 0; i < r; ++i)
         for (int k = 0; k < d; ++k) coords[v[i]][k] = coords_A[a][k] + r_A[a] * (nc[i][k] / mx);
     }
+  };
+}
+
+// anyToMultilevel(embedViaMinimization) with ITER sweeps as one libge call
+// (ge_embed_via_minimization_ml): every aggregate of the level in one batched
+// device launch, the same bits as the composition above.  Opt-in: pass it to
+// embedVia / embedViaMultilevel in place of anyToMultilevel(embedViaMinimization).
+inline MultilevelEmbedder minimizationToMultilevel(int ITER = 1000) {
+  return [ITER](const SparseMatrix& A, const SparseMatrix& P_T, const std::vector<int>& v_A,
+                const std::vector<std::vector<double>>& coords_A, const std::vector<double>& r_A,
+                std::vector<std::vector<double>>& coords, const int d) {
+    const int n = A.Rows(), m = P_T.Rows();
+    if ((int)v_A.size() != n || (int)r_A.size() != m || (int)coords_A.size() != m)
+      throw std::invalid_argument("minimizationToMultilevel: sizes do not match A and P_T");
+    const std::vector<double> cA = detail::flatten(coords_A, m, d);
+    std::vector<double> X((size_t)n * d);
+    detail::check(ge_embed_via_minimization_ml(
+        detail::context(), n, A.GetIndptr().data(), A.GetIndices().data(), m,
+        P_T.GetIndptr().data(), P_T.GetIndices().data(), v_A.data(), cA.data(), r_A.data(), d,
+        ITER, X.data(), nullptr));
+    detail::unflatten(X, n, d, coords);
   };
 }
 

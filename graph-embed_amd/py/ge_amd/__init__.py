@@ -13,6 +13,8 @@ Reference interfaces mirrored (LLNL/graph-embed):
   ptap               P_T.Mult(A).Mult(P_T.Transpose()) examples/embed.cpp:96-98
   embed              partition::embed                src/embed.cpp:561-796
   modularity         partition::modularity           src/partitioner.cpp:69-114
+  embed_via_minimization_ml  anyToMultilevel(embedViaMinimization), one level
+                                                     src/embed.cpp:23-83, :341-559
 """
 import ctypes
 import os
@@ -136,6 +138,9 @@ _SIGS = {
                                              _vp, _ip]),
     "ge_embed_via_minimization": (ctypes.c_int, [ctypes.c_int, _i32p, _i32p, ctypes.c_int, _f64p,
                                                  ctypes.c_int, ctypes.c_uint, ctypes.c_int]),
+    "ge_embed_via_minimization_ml": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int,
+                                                    _i32p, _i32p, _i32p, _f64p, _f64p,
+                                                    ctypes.c_int, ctypes.c_int, _f64p, _ip]),
     "ge_rmat_csr_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong,
                                           ctypes.c_int, ctypes.POINTER(_vp)]),
     "ge_largest_component_device": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p,
@@ -291,6 +296,9 @@ class Context:
             np.ascontiguousarray(r_A, dtype=np.float64), X.reshape(-1), dim, iterations,
             ctypes.byref(p)))
         return X
+
+    def embed_via_minimization_ml(self, A, PT, vertex_A, coords_A, r_A, dim, **kw):
+        return embed_via_minimization_ml(A, PT, vertex_A, coords_A, r_A, dim, ctx=self, **kw)
 
     def modularity(self, A, vertex_A, m):
         """partition::modularity with the O(nnz) pass on the device
@@ -809,6 +817,35 @@ def embed_via_minimization(A, dim, coords=None, iterations=10, seed=12345):
     _check(lib().ge_embed_via_minimization(n, ip, ix, dim, X.reshape(-1), int(coords is None),
                                            seed, iterations))
     return X
+
+
+def embed_via_minimization_ml(A, PT, vertex_A, coords_A, r_A, dim, iterations=1000, ctx=None,
+                              info=False):
+    """anyToMultilevel(embedViaMinimization) on one level (src/embed.cpp:23-83 over
+    :341-559): per aggregate of PT, `iterations` sweeps from a zero start on the
+    members' internal edges, normalised and placed in the aggregate's ball.  With a
+    Context the level is one batched device call; without one (or GE_MINIMIZE_HOST=1)
+    the library's host path, with the same bits.  info=True also returns the classes:
+    aggregates that ran packed / one wave per direction / on the host, and the path
+    (0 host, 1 device)."""
+    ip = np.ascontiguousarray(A[0], dtype=np.int32)
+    ix = np.ascontiguousarray(A[1], dtype=np.int32)
+    pip = np.ascontiguousarray(PT[0], dtype=np.int32)
+    pix = np.ascontiguousarray(PT[1], dtype=np.int32)
+    n, m = len(ip) - 1, len(pip) - 1
+    vA = np.ascontiguousarray(vertex_A, dtype=np.int32)
+    cA = np.ascontiguousarray(coords_A, dtype=np.float64).reshape(-1)
+    rA = np.ascontiguousarray(r_A, dtype=np.float64).reshape(-1)
+    if len(vA) != n or len(cA) != m * dim or len(rA) != m or len(pix) != n:
+        raise GeError("embed_via_minimization_ml: array sizes do not match n, m and dim")
+    X = np.zeros((n, dim))
+    classes = (ctypes.c_int * 4)()
+    _check(lib().ge_embed_via_minimization_ml(ctx.h if ctx is not None else None, n, ip, ix, m,
+                                              pip, pix, vA, cA, rA, dim, iterations,
+                                              X.reshape(-1), classes))
+    if not info:
+        return X
+    return X, dict(zip(("packed", "wave", "host", "path"), classes))
 
 
 def uniform_stream(seed, count):

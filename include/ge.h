@@ -365,12 +365,33 @@ int ge_embed_dist(ge_comm* comm, int levels, const int* a_n, const int* a_off,
  * search towards the 2d unit directions, then centring and scaling.  coords:
  * n*dim in/out; init_random != 0 first draws U(-1,1) from mt19937(seed) (the
  * reference's empty-coords branch, :353-361).  Edge weights are not read (the
- * reference ignores them).  Host code (off the embed path; the line searches are
- * chains of serial n-term sums); the 2d directions run on OpenMP threads.
+ * reference ignores them).  Host code (a single call is a chain of serial n-term
+ * sums); the 2d directions run on OpenMP threads.
  * anyToMultilevel / embedVia / embedViaMultilevel (src/embed.cpp:23-338) are
  * header-only in graph-embed_amd/include/embed.hpp on top of this ABI. */
 int ge_embed_via_minimization(int n, const int* indptr, const int* indices, int dim,
                               double* coords, int init_random, unsigned seed, int iterations);
+
+/* Replaces anyToMultilevel(embedViaMinimization)(A, P_T, v_A, coords_A, r_A, coords, d)
+ * (src/embed.cpp:23-83 over :341-559): per aggregate of P_T, `iterations` sweeps of
+ * the minimiser from a zero start on the members' internal edges, the result
+ * normalised by its largest norm and placed at coords_A[a] + r_A[a] * (x / max).
+ * iterations: the reference's two-argument overload uses 1000.  With a context the
+ * whole level is one batched device call (graph-embed_amd/csrc/ge_minimize_dev.hip)
+ * when the rows of A and of P_T are strictly ascending and dim <= 4; ctx == NULL,
+ * GE_MINIMIZE_HOST=1 or other inputs: the host path.  Same bits either way.  P_T
+ * must list every fine vertex once and vertex_A must be its inverse.  An aggregate
+ * with one member or without internal edges ends at NaN, as in the reference.
+ * classes (may be NULL) receives the aggregates that ran packed (one lane per
+ * direction), one wave per direction, and on the host (all of them on the host
+ * path; on the device path those beyond the LDS capacity), then the path (0 host,
+ * 1 device).  GE_MIN_PACK_MAX (largest packed aggregate, 0..64), GE_MIN_LDS_BYTES
+ * (LDS capacity, at most the device's) and GE_MIN_WAVES (waves of a block) override
+ * the class rule.  Diagnostics; the results do not depend on them. */
+int ge_embed_via_minimization_ml(ge_ctx* ctx, int n, const int* indptr, const int* indices,
+                                 int m, const int* pt_indptr, const int* pt_indices,
+                                 const int* vertex_A, const double* coords_A, const double* r_A,
+                                 int dim, int iterations, double* coords, int* classes);
 
 /* The reference's initial-coordinate stream: the first `count` values of
  * uniform_real_distribution<double>(-1,1) over mt19937(seed) (libstdc++). */
