@@ -498,7 +498,7 @@ int ge_force_atlas_dist(ge_comm* c, int n, const int* ip, const int* ix, const d
   return guarded([&] {
     ge::check_comm(c);
     GE_REQUIRE(p && (coords || n == 0), "null argument");
-    GE_REQUIRE(dim >= 1 && dim <= 4, "dimension must be 1..4");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
     GE_REQUIRE(iterations >= 0, "negative iteration count");
     GE_REQUIRE(n == 0 || (ip && ix && dx && ip[0] == 0), "bad CSR");
     if (n > 0) ge::check_csr(n, ip, ix, dx);  // indices in range, as the one-GPU calls
@@ -514,7 +514,7 @@ int ge_force_atlas_ml_dist(ge_comm* c, int n, const int* ip, const int* ix, cons
   return guarded([&] {
     ge::check_comm(c);
     GE_REQUIRE(p && pip && pix && vA && cA && rA && (coords || n == 0), "null argument");
-    GE_REQUIRE(dim >= 1 && dim <= 4, "dimension must be 1..4");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
     GE_REQUIRE(n == 0 || (ip && ix && dx && ip[0] == 0), "bad CSR");
     if (n > 0) ge::check_csr(n, ip, ix, dx);  // indices in range, as the one-GPU calls
     GE_REQUIRE(m >= 0 && pip[0] == 0 && pip[m] == n, "P_T must have one entry per fine vertex");

@@ -29,6 +29,11 @@
 //
 // Small graphs (n <= 1024, e.g. the coarsest level, 1e5 iterations) run all
 // iterations inside one workgroup with coordinates resident in LDS.
+//
+// Dimensions 5..16 run the wide schedule (ge_pair.hpp): fa_small_strict's general
+// form for n <= 64 (GE_SMALL_MAX: up to 256), fa_grouped_step /
+// fa_grouped_stream for n <= stream_max (graph replay for long runs), else
+// fa_repulse_strict<D, false, 1> and the CSR row kernels; LDS capacities per D.
 
 #include <hip/hip_runtime.h>
 
@@ -89,11 +94,14 @@ __global__ void degp1_kernel(int n, const int* __restrict__ ip, const double* __
 
 constexpr int kRepThreads = 512;
 constexpr int kTileJ = 256;
-constexpr int kRepRU = 8;  // row slots x partners in flight per lane
+// Row slots x partners in flight per lane.  A lane holds xi, acc and the terms in
+// flight, D doubles each: 8 up to D = 4, then 2 and 1 so that the terms in flight stay
+// within 16 doubles and the kernel in registers.
+constexpr int rep_ru(int D) { return D <= kNarrowMaxDim ? 8 : D <= 8 ? 2 : 1; }
 
 template <int D>
 struct Rec {
-  static constexpr int W = (D + 1 <= 4) ? 4 : 8;  // doubles per LDS record
+  static constexpr int W = rec_width(D);  // doubles per LDS record
 };
 
 // One LDS tile of partners for the first NR row slots of a wave (NR is the
@@ -148,7 +156,8 @@ __global__ void __launch_bounds__(kRepThreads)
 fa_repulse_strict(int n, int rb, int re, int per_block, const double* __restrict__ X,
                   const double* __restrict__ dp1, double repel, double* __restrict__ Frep) {
   constexpr int W = Rec<D>::W;
-  constexpr int U = kRepRU / R;
+  static_assert(rep_ru(D) % R == 0, "R row slots divide the pairs in flight");
+  constexpr int U = rep_ru(D) / R;
   __shared__ __attribute__((aligned(16))) double tile[kTileJ * W];
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -418,6 +427,19 @@ struct FaRows {
 // lane per row (n = 127 gives 16 waves instead of 2).
 
 constexpr int kSmallMax = 512;  // one row group per thread group below
+// Above D = 4 (the wide schedule) the general kernel alone runs, with kSmallWideT
+// threads: 512 threads leave 256 registers per lane, and the kernel holds xi, acc, F
+// and fprev (D doubles each) beside a term.  Its rows are what the block's LDS leaves
+// for records after the term buffer of kSmallWideT x D doubles, at most one row per
+// thread: 256 at every D up to 16 (the LDS alone would allow 903 at D = 16).  Larger
+// levels take the fused step.
+constexpr int kSmallWideT = 256;
+constexpr int small_cap(int D) {
+  if (D <= kNarrowMaxDim) return kSmallMax;
+  const size_t rows = (kLdsBlock - sizeof(double) * kSmallWideT * D) / (sizeof(double) * rec_width(D));
+  return rows < (size_t)kSmallWideT ? (int)rows : kSmallWideT;
+}
+static_assert(small_cap(5) == 256 && small_cap(16) == 256, "one row per thread fits at every D");
 constexpr int kSmallDefault = 64;
 constexpr int kSmallNnz = 6144;
 // CSR entries staged in LDS (the 4-D double-buffered term tile leaves less room)
@@ -559,7 +581,7 @@ fa_small_strict(int n, const int* __restrict__ ip, const int* __restrict__ ixg,
                 int iterations, int stop_at, FaConst c) {
   constexpr int W = Rec<D>::W;
   constexpr int U = 1;
-  __shared__ __attribute__((aligned(16))) double sx[kSmallMax * W];
+  __shared__ __attribute__((aligned(16))) double sx[small_cap(D) * W];
   __shared__ __attribute__((aligned(16))) double tb[(G > 1 ? T * U * (DOMAIN_ONLY ? 2 : 1) : 1) * D];
   __shared__ int s_ix[STAGED ? small_nnz_cap(D) : 1];
   __shared__ double s_dx[STAGED ? small_nnz_cap(D) : 1];
@@ -786,6 +808,26 @@ void launch_small(hipStream_t s, int n, int nnz, const int* ip, const int* ix, c
   by_group(small_group(n, kSmallGenT), std::integral_constant<int, kSmallGenT>(), F());
 }
 
+// The wide schedule's one-workgroup run: the general kernel from iteration 0 (both
+// bodies, CSR read from global memory), kSmallWideT threads, 1, 2 or 8 lanes per row.
+inline int small_wide_cap(int D) { return std::min(small_cap(D), kSmallWideT); }
+template <int D>
+void launch_small_wide(hipStream_t s, int n, const int* ip, const int* ix, const double* dx,
+                       const double* dp1, double* X, double* Fp, int* it_state, int iterations,
+                       const FaConst& c) {
+  GE_HIP(hipMemsetAsync(Fp, 0, sizeof(double) * (size_t)n * D, s));
+  GE_HIP(hipMemsetAsync(it_state, 0, sizeof(int), s));
+  auto go = [&](auto GG) {
+    hipLaunchKernelGGL((fa_small_strict<D, decltype(GG)::value, kSmallWideT, false, false>),
+                       dim3(1), dim3(kSmallWideT), 0, s, n, ip, ix, dx, dp1, X, Fp, it_state,
+                       iterations, iterations, c);
+  };
+  const int G = small_group(n, kSmallWideT);  // n G <= kSmallWideT
+  if (G >= 8) go(std::integral_constant<int, 8>());
+  else if (G >= 2) go(std::integral_constant<int, 2>());
+  else go(std::integral_constant<int, 1>());
+}
+
 // ---------------------------------------------------------------------------
 // STRICT repulsion for small n (n <= grouped_cap, e.g. the coarsest levels of
 // configs[3]): too few rows to fill the chip one lane per row, so G lanes share
@@ -797,11 +839,14 @@ void launch_small(hipStream_t s, int n, int nnz, const int* ip, const int* ix, c
 // the T threads of the block: SU records per thread per round with all their
 // loads issued before the stores (a plain strided loop waits for one record at
 // a time).  Returns whether every staged value lies in the exact-division domain.
-template <int D, int T, int SU, bool COH = false>
+// (SU0 is the count up to D = 4; wider records take 4 SU0 / D, at least one, so the
+// values in flight per thread do not grow with D.)
+template <int D, int T, int SU0, bool COH = false>
 __device__ __forceinline__ bool stage_records(const double* __restrict__ X,
                                               const double* __restrict__ dp1, int first, int cnt,
                                               double* rec) {
   constexpr int W = Rec<D>::W;
+  constexpr int SU = D <= kNarrowMaxDim ? SU0 : (4 * SU0 / D > 1 ? 4 * SU0 / D : 1);
   bool ok = true;
   for (int q0 = 0; q0 < cnt; q0 += T * SU) {
     double v[SU][D + 1];
@@ -850,9 +895,19 @@ __device__ __forceinline__ bool stage_records(const double* __restrict__ X,
 constexpr bool kBarCohStage = GE_BAR_ORDER < 3;
 
 constexpr int kGrpT = 256;
-constexpr int grouped_cap(int D) { return (D + 1 <= 4) ? 3072 : 1536; }  // <= 96 KiB of records
+// LDS of the fused step: the records (rec_width(D) doubles each), then the two term
+// buffers of kGrpT x D doubles.  The records get what the block's LDS leaves after the
+// term buffers, at most 96 KiB: 3072 records at D <= 3, 1536 at D = 4..7, 675 at D = 16.
+constexpr size_t grouped_tb_bytes(int D) { return sizeof(double) * 2 * kGrpT * D; }
+constexpr size_t grouped_rec_budget(int D) {
+  return kLdsBlock - grouped_tb_bytes(D) < 96 * 1024 ? kLdsBlock - grouped_tb_bytes(D) : 96 * 1024;
+}
+constexpr int grouped_cap(int D) {
+  return (int)(grouped_rec_budget(D) / (sizeof(double) * rec_width(D)));
+}
+static_assert(grouped_cap(3) == 3072 && grouped_cap(4) == 1536, "the D <= 4 caps are unchanged");
 inline size_t grouped_lds_bytes(int n, int D) {
-  return sizeof(double) * ((size_t)n * ((D + 1 <= 4) ? 4 : 8) + 2 * kGrpT * D);
+  return sizeof(double) * (size_t)n * rec_width(D) + grouped_tb_bytes(D);
 }
 
 template <int D, int G, bool REPEL_ONE>
@@ -1034,7 +1089,7 @@ constexpr int kPackC = 96;  // partners per row per chunk
 // 10.2 us per iteration (0.85 us per chunk of 96 partners) against ~0.3 us of adds.
 constexpr int kPackS = kPackC + 2;
 inline size_t packed_lds_bytes(int n, int D, int R) {
-  return sizeof(double) * ((size_t)n * ((D + 1 <= 4) ? 4 : 8) + 2 * (size_t)R * D * kPackS);
+  return sizeof(double) * ((size_t)n * rec_width(D) + 2 * (size_t)R * D * kPackS);
 }
 
 // group_chain for the packed adder lane: the first nb batches (of 16 terms) of a chunk,
@@ -1323,16 +1378,19 @@ fa_grouped_persistent(int n, const int* __restrict__ ip, const int* __restrict__
 // with the records streamed through LDS in tiles of kStreamTile (the in-domain
 // test per tile, the attraction's neighbours read from X), so a coarsest level
 // of a few thousand to tens of thousands of vertices keeps G lanes per row.
-constexpr int kStreamTile = 2048;
+// Records per tile: 2048 while they fit beside the term buffers, else the largest
+// multiple of 256 within grouped_cap(D) (D = 5..7: 1536, D = 8: 1024, D = 16: 512).
+constexpr int stream_tile(int D) {
+  return grouped_cap(D) >= 2048 || D <= kNarrowMaxDim ? 2048 : grouped_cap(D) / 256 * 256;
+}
+static_assert(stream_tile(16) >= 256, "a tile of at least one round of the block");
 constexpr int kStreamMax = 65536;
 // GE_STREAM_MAX overrides the bound (tuning / tests)
 inline int stream_max() {
   if (const char* e = std::getenv("GE_STREAM_MAX")) return std::atoi(e);
   return kStreamMax;
 }
-inline size_t stream_lds_bytes(int D) {
-  return sizeof(double) * ((size_t)kStreamTile * ((D + 1 <= 4) ? 4 : 8) + 2 * kGrpT * D);
-}
+inline size_t stream_lds_bytes(int D) { return grouped_lds_bytes(stream_tile(D), D); }
 
 template <int D, int G, bool REPEL_ONE, bool LINEAR>
 __global__ void __launch_bounds__(kGrpT)
@@ -1341,6 +1399,7 @@ fa_grouped_stream(int n, int rb, int re, const int* __restrict__ ip, const int* 
                   const double* __restrict__ dp1, FaConst c, double* __restrict__ Fprev,
                   double* __restrict__ Xnext) {
   constexpr int W = Rec<D>::W;
+  constexpr int kStreamTile = stream_tile(D);
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* rec = smem;
   double* tb = smem + (size_t)kStreamTile * W;
@@ -1448,11 +1507,23 @@ inline int grouped_lanes(int rows) {
   return G;
 }
 
+// fa_repulse_strict's grid: one block per CU, rows split evenly (rounded to whole
+// 64-row wave slots).  GE_REP_BLOCKS caps the blocks (tests).
+inline void rep_grid(int rows, int cus, int& per, int& nb) {
+  int cap = cus;
+  if (const char* e = std::getenv("GE_REP_BLOCKS")) cap = std::max(1, std::atoi(e));  // tests
+  const int blocks = std::max(1, std::min(cap, (rows + 63) / 64));
+  per = (rows + blocks - 1) / blocks;
+  per = (per + 63) / 64 * 64;
+  nb = (rows + per - 1) / per;
+}
+
+// The schedules of D <= kNarrowMaxDim.
 template <int D>
-void launch_repulsion(hipStream_t s, int mode, int n, int rb, int re, const double* X,
-                      const double* dp1, double repel, double* Frep, double* Fpart, int cus) {
+void launch_repulsion_narrow(hipStream_t s, int mode, int n, int rb, int re, const double* X,
+                             const double* dp1, double repel, double* Frep, double* Fpart,
+                             int cus) {
   const int rows = re - rb;
-  if (rows <= 0) return;
   if (mode == GE_MODE_FAST) {
     const int per = kFastThreads * kRowsPerThreadFast;
     const int jb = std::max(1, std::min(kFastJBlocks, (n + kTileJ - 1) / kTileJ));
@@ -1496,13 +1567,8 @@ void launch_repulsion(hipStream_t s, int mode, int n, int rb, int re, const doub
     }
     return;
   }
-  // one block per CU, rows split evenly (rounded to whole 64-row wave slots)
-  int cap = cus;
-  if (const char* e = std::getenv("GE_REP_BLOCKS")) cap = std::max(1, std::atoi(e));  // tests
-  const int blocks = std::max(1, std::min(cap, (rows + 63) / 64));
-  int per = (rows + blocks - 1) / blocks;
-  per = (per + 63) / 64 * 64;
-  const int nb = (rows + per - 1) / per;
+  int per, nb;
+  rep_grid(rows, cus, per, nb);
   // Row slots per lane.  Measured at C2 size (scripts/shard_tune.py, rows of
   // an N-GPU shard): with more than 1024 rows per block 8 slots x 1 partner is
   // fastest (500 K rows: 581 against 563 Gpairs/s for R = 1); at 1024 and below
@@ -1530,44 +1596,68 @@ void launch_repulsion(hipStream_t s, int mode, int n, int rb, int re, const doub
   }
 }
 
-// Small levels (n <= grouped_cap: fa_grouped_step) and mid-size ones (n <=
-// stream_max: fa_grouped_stream): one launch per iteration.
+// wide: the ordered-pair kernel at every size, one row slot per lane (ge_pair.hpp).
 template <int D>
-void launch_grouped_step(hipStream_t s, int n, int rb, int re, const int* ip, const int* ix,
-                         const double* dx, const double* X, const double* dp1, const FaConst& c,
-                         double* Fprev, double* Xnext) {
+void launch_repulsion(hipStream_t s, int mode, int n, int rb, int re, const double* X,
+                      const double* dp1, double repel, double* Frep, double* Fpart, int cus,
+                      bool wide) {
   const int rows = re - rb;
   if (rows <= 0) return;
-  const bool stream = n > grouped_cap(D);
-  const size_t lds = stream ? stream_lds_bytes(D) : grouped_lds_bytes(n, D);
+  if (wide || D > kNarrowMaxDim) {
+    int per, nb;
+    rep_grid(rows, cus, per, nb);
+    hipLaunchKernelGGL((fa_repulse_strict<D, false, 1>), dim3(nb), dim3(kRepThreads), 0, s, n, rb,
+                       re, per, X, dp1, repel, Frep);
+    return;
+  }
+  if constexpr (D <= kNarrowMaxDim)
+    launch_repulsion_narrow<D>(s, mode, n, rb, re, X, dp1, repel, Frep, Fpart, cus);
+}
+
+// Small levels (n <= grouped_cap: fa_grouped_step) and mid-size ones (n <=
+// stream_max: fa_grouped_stream): one launch per iteration.
+struct GroupedArgs {
+  hipStream_t s;
+  int n, rb, re;
+  const int *ip, *ix;
+  const double *dx, *X, *dp1;
+  const FaConst& c;
+  double *Fprev, *Xnext;
+};
+
+template <int D, int GC, bool R1, bool LIN>
+void launch_grouped_variant(const GroupedArgs& a) {
+  const int rows = a.re - a.rb;
+  const bool stream = a.n > grouped_cap(D);
+  const size_t lds = stream ? stream_lds_bytes(D) : grouped_lds_bytes(a.n, D);
+  const int nb = (rows + kGrpT / GC - 1) / (kGrpT / GC);
+  const void* fn = stream ? reinterpret_cast<const void*>(&fa_grouped_stream<D, GC, R1, LIN>)
+                          : reinterpret_cast<const void*>(&fa_grouped_step<D, GC, R1, LIN>);
+  if (lds > 65536)  // above the default dynamic-LDS limit
+    GE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (stream)
+    hipLaunchKernelGGL((fa_grouped_stream<D, GC, R1, LIN>), dim3(nb), dim3(kGrpT), lds, a.s, a.n,
+                       a.rb, a.re, a.ip, a.ix, a.dx, a.X, a.dp1, a.c, a.Fprev, a.Xnext);
+  else
+    hipLaunchKernelGGL((fa_grouped_step<D, GC, R1, LIN>), dim3(nb), dim3(kGrpT), lds, a.s, a.n,
+                       a.rb, a.re, a.ip, a.ix, a.dx, a.X, a.dp1, a.c, a.Fprev, a.Xnext);
+}
+
+// D <= kNarrowMaxDim: every group size, the repel == 1 and linear-attraction bodies.
+template <int D>
+void launch_grouped_step_narrow(const GroupedArgs& a) {
   auto go = [&](auto GG) {
     constexpr int GC = decltype(GG)::value;
-    const int nb = (rows + kGrpT / GC - 1) / (kGrpT / GC);
-    auto one = [&](auto RO, auto LI) {
-      constexpr bool R1 = decltype(RO)::value, LIN = decltype(LI)::value;
-      const void* fn = stream ? reinterpret_cast<const void*>(&fa_grouped_stream<D, GC, R1, LIN>)
-                              : reinterpret_cast<const void*>(&fa_grouped_step<D, GC, R1, LIN>);
-      if (lds > 65536)  // above the default dynamic-LDS limit
-        GE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      if (stream)
-        hipLaunchKernelGGL((fa_grouped_stream<D, GC, R1, LIN>), dim3(nb), dim3(kGrpT), lds, s, n,
-                           rb, re, ip, ix, dx, X, dp1, c, Fprev, Xnext);
-      else
-        hipLaunchKernelGGL((fa_grouped_step<D, GC, R1, LIN>), dim3(nb), dim3(kGrpT), lds, s, n,
-                           rb, re, ip, ix, dx, X, dp1, c, Fprev, Xnext);
-    };
-    const bool lin = !c.linlog && c.delta == 1.0;
-    using T = std::true_type;
-    using F = std::false_type;
-    if (c.repel == 1.0) {
-      if (lin) one(T(), T());
-      else one(T(), F());
+    const bool lin = !a.c.linlog && a.c.delta == 1.0;
+    if (a.c.repel == 1.0) {
+      if (lin) launch_grouped_variant<D, GC, true, true>(a);
+      else launch_grouped_variant<D, GC, true, false>(a);
     } else {
-      if (lin) one(F(), T());
-      else one(F(), F());
+      if (lin) launch_grouped_variant<D, GC, false, true>(a);
+      else launch_grouped_variant<D, GC, false, false>(a);
     }
   };
-  switch (grouped_lanes(rows)) {
+  switch (grouped_lanes(a.re - a.rb)) {
     case 64: go(std::integral_constant<int, 64>()); break;
     case 32: go(std::integral_constant<int, 32>()); break;
     case 16: go(std::integral_constant<int, 16>()); break;
@@ -1576,6 +1666,22 @@ void launch_grouped_step(hipStream_t s, int n, int rb, int re, const int* ip, co
     case 2: go(std::integral_constant<int, 2>()); break;
     default: go(std::integral_constant<int, 1>()); break;
   }
+}
+
+// wide (ge_pair.hpp): the general bodies (same bits as their specialisations) in two
+// group sizes, a wave per row below 8192 rows (grouped_lanes 32 or 64), else 8 lanes.
+template <int D>
+void launch_grouped_step(hipStream_t s, int n, int rb, int re, const int* ip, const int* ix,
+                         const double* dx, const double* X, const double* dp1, const FaConst& c,
+                         double* Fprev, double* Xnext, bool wide) {
+  if (re - rb <= 0) return;
+  const GroupedArgs a{s, n, rb, re, ip, ix, dx, X, dp1, c, Fprev, Xnext};
+  if (wide || D > kNarrowMaxDim) {
+    if (grouped_lanes(re - rb) >= 32) launch_grouped_variant<D, 64, false, false>(a);
+    else launch_grouped_variant<D, 8, false, false>(a);
+    return;
+  }
+  if constexpr (D <= kNarrowMaxDim) launch_grouped_step_narrow<D>(a);
 }
 
 template <int D>
@@ -1605,6 +1711,7 @@ struct ge_fa_plan {
   ge::RowClasses rc;
   ge::RowStreams rstreams;
   int cus = 256;
+  bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
   bool profiling = false;
   std::vector<hipEvent_t> events;  // 3 per timed step
   size_t next_event = 0;
@@ -1630,6 +1737,9 @@ namespace ge {
 static void plan_init(ge_fa_plan* pl) {
   const int rows = pl->re - pl->rb;
   pl->cus = device_cus();
+  pl->wide = wide_dim(pl->dim);
+  // FAST is a tolerance-only mode and has no wide kernels: the exact ones satisfy it
+  if (pl->wide) pl->p.mode = GE_MODE_STRICT;
   pl->dp1.alloc(pl->n);
   pl->frep.alloc((size_t)std::max(rows, 1) * pl->dim);
   pl->fprev.alloc((size_t)std::max(rows, 1) * pl->dim);
@@ -1664,8 +1774,8 @@ static void plan_init(ge_fa_plan* pl) {
   {
     const char* e = std::getenv("GE_FA_SYM");
     const bool force = e && *e == '1', off = e && *e == '0';
-    pl->sym = !off && pl->p.mode == GE_MODE_STRICT && pl->rb == 0 && pl->re == pl->n &&
-              (force || pl->n > stream_max());
+    pl->sym = !off && !pl->wide && pl->p.mode == GE_MODE_STRICT && pl->rb == 0 &&
+              pl->re == pl->n && (force || pl->n > stream_max());
   }
   // (Round 4 also built a degree-ordered gather copy of the coordinates for the
   // neighbour gathers: C2 0.324 against 0.301 ms per pass, C5 31.8 against 30.3 ms;
@@ -1732,11 +1842,11 @@ static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
     constexpr int D = decltype(Dc)::value;
     if (pl->p.mode == GE_MODE_STRICT && pl->n <= stream_max() && !std::getenv("GE_GRP_SPLIT")) {
       launch_grouped_step<D>(s, pl->n, pl->rb, pl->re, pl->ip, pl->ix, pl->dx, xc, pl->dp1.p,
-                             pl->c, pl->fprev.p, xn);
+                             pl->c, pl->fprev.p, xn, pl->wide);
       if (ev) GE_HIP(hipEventRecord(ev[1], s));
       return;
     }
-    if (pl->sym) {
+    if (pl->sym) {  // never on the wide schedule (plan_init)
       sym_prepare(pl);
       sym_check(pl);
       GE_HIP(hipMemsetAsync(pl->ctl.p, 0, sizeof(int) * pl->ctl.n, s));
@@ -1745,7 +1855,7 @@ static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
                          (size_t)pl->n, pl->ctl.p + 1, pl->sym_err_d, pl->sym_limit);
     } else {
       launch_repulsion<D>(s, pl->p.mode, pl->n, pl->rb, pl->re, xc, pl->dp1.p, pl->p.repel,
-                          pl->frep.p, pl->fpart.p, pl->cus);
+                          pl->frep.p, pl->fpart.p, pl->cus, pl->wide);
     }
     if (ev) GE_HIP(hipEventRecord(ev[1], s));
     launch_attract<D>(s, pl->rc, pl->rstreams, pl->rb, pl->ip, pl->ix, pl->dx, xc, pl->dp1.p, pl->frep.p,
@@ -1939,16 +2049,28 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
   // against 26).  GE_SMALL_MAX moves the bound (tests use it up to kSmallMax).
   int small_max = kSmallDefault;
   if (const char* e = std::getenv("GE_SMALL_MAX")) small_max = std::min(kSmallMax, std::atoi(e));
-  if (n <= small_max && p.mode == GE_MODE_STRICT) {
+  // The wide schedule runs the one-workgroup kernel in its general form up to
+  // small_wide_cap(dim) rows (FAST runs the exact kernels there); it has no persistent
+  // kernel: above the bound its long runs replay a graph of fused steps (below).
+  const bool wide = wide_dim(dim);
+  if (wide) small_max = std::min(small_max, small_wide_cap(dim));
+  if (n <= small_max && (p.mode == GE_MODE_STRICT || wide)) {
     DevBuf<double> dp1(n), fp((size_t)n * dim);
     DevBuf<int> it_state(1);
     hipLaunchKernelGGL(degp1_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, d_ip, d_dx,
                        p.use_weights, dp1.p);
     FaConst c = make_const(p);
-    dispatch_dim(dim, [&](auto Dc) {
-      constexpr int D = decltype(Dc)::value;
-      launch_small<D>(s, n, nnz, d_ip, d_ix, d_dx, dp1.p, d_x, fp.p, it_state.p, iterations, c);
-    });
+    if (wide) {
+      dispatch_dim(dim, [&](auto Dc) {
+        launch_small_wide<decltype(Dc)::value>(s, n, d_ip, d_ix, d_dx, dp1.p, d_x, fp.p,
+                                               it_state.p, iterations, c);
+      });
+    } else {
+      dispatch_dim_narrow(dim, [&](auto Dc) {
+        constexpr int D = decltype(Dc)::value;
+        launch_small<D>(s, n, nnz, d_ip, d_ix, d_dx, dp1.p, d_x, fp.p, it_state.p, iterations, c);
+      });
+    }
     GE_HIP(hipGetLastError());
     GE_HIP(hipStreamSynchronize(s));
     return;
@@ -1971,9 +2093,10 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
   double* cur = d_x;
   double* nxt = other.p;
   int it = 0;
-  if (p.mode == GE_MODE_STRICT && iterations >= kPersistMin && !std::getenv("GE_NO_PERSIST")) {
+  if (p.mode == GE_MODE_STRICT && iterations >= kPersistMin && !wide &&
+      !std::getenv("GE_NO_PERSIST")) {
     bool done = false;
-    dispatch_dim(dim, [&](auto Dc) {
+    dispatch_dim_narrow(dim, [&](auto Dc) {
       done = launch_persistent<decltype(Dc)::value>(&pl, d_x, other.p, iterations);
     });
     if (done) {
@@ -2026,7 +2149,7 @@ int ge_fa_plan_create(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d
                       ge_fa_plan** out) {
   return ge::guarded([&] {
     GE_REQUIRE(ctx && p && out, "null argument");
-    GE_REQUIRE(n > 0 && dim >= 1 && dim <= 4, "bad n or dim (dim must be 1..4)");
+    GE_REQUIRE(n > 0 && dim >= 1 && dim <= ge::kMaxDim, "bad n or dim (dim must be 1..16)");
     GE_REQUIRE(0 <= rb && rb <= re && re <= n, "bad row range");
     ge::DeviceGuard g(ctx);
     auto* pl = new ge_fa_plan();

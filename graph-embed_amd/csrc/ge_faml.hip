@@ -12,10 +12,13 @@
 // Aggregates are bucketed by size s:
 //   s <= 64          packs of aggregates with <= 64 members total, 64-thread block
 //   64 < s <= 256    packs with <= 256 members, 256-thread block
-//   256 < s <= 4096  one aggregate per 256-thread block
+//   256 < s <= cap   one aggregate per 256-thread block; cap = large_cap(dim): 4096
+//                    members at dim <= 3, 2048 at dim 4..7, ..., 874 at dim 16
 //   (all three: coordinates resident in LDS, all iterations in ONE launch)
-//   s > 4096         "streamed": per iteration a force kernel (j tiles through
+//   s > cap          "streamed": per iteration a force kernel (j tiles through
 //                    LDS) and an update kernel, coordinates in HBM.
+// Dimensions 5..16 run the wide schedule (ge_pair.hpp): the same resident kernels,
+// and the streamed aggregates on faml_big_repulse<D, 1, 1> (no symmetric sweeps).
 //
 // STRICT op order, as ge_fa.hip: per member the j loop runs over the aggregate's
 // members in P_T order (:394-410), then the CSR row in stored order with the
@@ -50,11 +53,21 @@ using MlConst = FaConst;
 
 template <int D>
 struct W {
-  static constexpr int v = (D + 1 <= 4) ? 4 : 8;
+  static constexpr int v = rec_width(D);
 };
 
-// Largest aggregate kept resident in LDS (128 KiB of member records).
-constexpr int large_cap(int dim) { return dim + 1 <= 4 ? 4096 : 2048; }
+// Largest aggregate kept resident in LDS: 128 KiB of member records (rec_width(D)
+// doubles each), or what the block's LDS leaves after faml_resident's other arrays
+// (the 257 + 256 pack offsets and the 256 x (D + 1) doubles of centres) where that
+// is less: 4096 members at D <= 3, 2048 at D = 4..7, 1638 at D = 8, 874 at D = 16.
+constexpr size_t resident_fixed_bytes(int dim) {
+  return sizeof(int) * (2 * 256 + 1) + sizeof(double) * 256 * (dim + 1) + 16;
+}
+constexpr int large_cap(int dim) {
+  const size_t left = kLdsBlock - resident_fixed_bytes(dim);
+  return (int)((left < 128 * 1024 ? left : 128 * 1024) / (sizeof(double) * rec_width(dim)));
+}
+static_assert(large_cap(3) == 4096 && large_cap(4) == 2048, "the D <= 4 caps are unchanged");
 
 // Internal degree + 1 of member at position c in aggregate a (:362-383).
 __device__ __forceinline__ double internal_dp1(int v, int a, const int* __restrict__ ip,
@@ -666,10 +679,29 @@ void build_packs(const std::vector<int>& ids, const int* h_pt_ip, int cap, int m
 #define GE_BIG_VARIANTS(X) X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(4, 1)
 constexpr int big_code(int R, int U) { return R * 8 + U; }
 
+template <int D>  // the variants of D <= kNarrowMaxDim (below)
+void launch_big_repulse_narrow(int code, int blocks, hipStream_t st, int nitems,
+                               const int2* items, int* queue, const int* pt_ip, const double* X,
+                               const double* DP, double repel, double* F);
+
 template <int D>
 void launch_big_repulse(int code, int blocks, hipStream_t st, int nitems, const int2* items,
                         int* queue, const int* pt_ip, const double* X, const double* DP,
-                        double repel, double* F) {
+                        double repel, double* F, bool wide) {
+  if (wide || D > kNarrowMaxDim) {  // the wide schedule's one variant (faml_plan_build)
+    if (code != big_code(1, 1)) throw Error(GE_ERR_STATE, "unknown streamed repulsion variant");
+    hipLaunchKernelGGL((faml_big_repulse<D, 1, 1, false>), dim3(blocks), dim3(kHT), 0, st, nitems,
+                       items, queue, pt_ip, X, DP, repel, F);
+    return;
+  }
+  if constexpr (D <= kNarrowMaxDim) launch_big_repulse_narrow<D>(code, blocks, st, nitems, items,
+                                                                 queue, pt_ip, X, DP, repel, F);
+}
+
+template <int D>
+void launch_big_repulse_narrow(int code, int blocks, hipStream_t st, int nitems,
+                               const int2* items, int* queue, const int* pt_ip, const double* X,
+                               const double* DP, double repel, double* F) {
   switch (code) {
 #define GE_BIG_LAUNCH(RR, UU)                                                                 \
   case big_code(RR, UU):                                                                      \
@@ -692,13 +724,15 @@ int rep_occupancy(int dim, int code) {
   int nb = 1;
   dispatch_dim(dim, [&](auto Dc) {
     constexpr int D = decltype(Dc)::value;
-    const void* k = nullptr;
-    switch (code) {
+    const void* k = (const void*)faml_big_repulse<D, 1, 1, false>;
+    if constexpr (D <= kNarrowMaxDim) {
+      switch (code) {
 #define GE_BIG_KERNEL(RR, UU) \
   case big_code(RR, UU): k = (const void*)faml_big_repulse<D, RR, UU, false>; break;
-      GE_BIG_VARIANTS(GE_BIG_KERNEL)
+        GE_BIG_VARIANTS(GE_BIG_KERNEL)
 #undef GE_BIG_KERNEL
-      default: k = (const void*)faml_big_repulse<D, 1, 1, false>;
+        default: break;
+      }
     }
     GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kHT, 0));
   });
@@ -728,6 +762,7 @@ struct ge_faml_plan {
   int nrows = 0, nitems = 0, R = 1, code = 0, rep_blocks = 0;
   // symmetric repulsion (ge_sym.hpp): sweep units and per-tile progress counters
   bool sym = false;
+  bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
   ge::DevBuf<int4> units;
   ge::DevBuf<int> prog;
   ge::DevBuf<double> hand;  // column sums handed between sweeps, component-major [dim][n]
@@ -856,7 +891,9 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
 #define GE_BIG_KNOWN(RR, UU) known = known || (R == RR && U == UU);
   GE_BIG_VARIANTS(GE_BIG_KNOWN)
 #undef GE_BIG_KNOWN
-  if (!known) {
+  // the wide schedule (ge_pair.hpp) has the one variant, and no symmetric sweeps
+  const bool wide = pl->wide = wide_dim(dim);
+  if (!known || wide) {
     R = kBigDefaultR;
     U = kBigDefaultU;
   }
@@ -911,7 +948,7 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   // earliest start (2A tile-times into the aggregate), larger aggregates first
   {
     const char* e = std::getenv("GE_FAML_SYM");
-    pl->sym = !(e && *e == '0');
+    pl->sym = !(e && *e == '0') && !wide;
   }
   if (pl->sym && (!big.empty() || !split.empty())) {
     // The sweeps of an aggregate with T row tiles form a chain of ~2.5 T tile-times
@@ -923,7 +960,7 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
     const bool any_big = !big.empty();
     for (size_t b = 0; b < big.size(); ++b) T[b] = (h_pt_ip[big[b] + 1] - h_pt_ip[big[b]] + 63) / 64;
     int occ = 1;
-    dispatch_dim(dim, [&](auto Dc) {
+    dispatch_dim_narrow(dim, [&](auto Dc) {
       constexpr int D = decltype(Dc)::value;
       GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &occ, (const void*)faml_sym_repulse<D, false>, kSymT, 0));
@@ -1225,10 +1262,11 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
           int* err = pl->sym_err.p;
           const long long lim = pl->sym_limit;
           if (!pl->stamp_path.empty()) {
-            hipLaunchKernelGGL((faml_sym_repulse<D, false, true>), dim3(pl->sym_blocks),
-                               dim3(kSymT), 0, ss, pl->nunits, pl->units.p, pl->queue.p + it,
-                               pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p, H, hs, pl->prog.p,
-                               err, lim, pl->stamps.p);
+            if constexpr (D <= kNarrowMaxDim)  // sym is never set on the wide schedule
+              hipLaunchKernelGGL((faml_sym_repulse<D, false, true>), dim3(pl->sym_blocks),
+                                 dim3(kSymT), 0, ss, pl->nunits, pl->units.p, pl->queue.p + it,
+                                 pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p, H, hs, pl->prog.p,
+                                 err, lim, pl->stamps.p);
           } else {
             sym_repulse_launch(D, pl->sym_blocks, ss, pl->nunits, pl->units.p, pl->queue.p + it,
                                pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p, H, hs, pl->prog.p,
@@ -1236,7 +1274,8 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
           }
         } else {
           launch_big_repulse<D>(pl->code, pl->rep_blocks, ss, pl->nitems, pl->items.p,
-                                pl->queue.p + it, pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p);
+                                pl->queue.p + it, pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p,
+                                pl->wide);
         }
         if (re) GE_HIP(hipEventRecord(re[1], ss));
         hipEvent_t* ae = nullptr;
@@ -1300,7 +1339,7 @@ void sym_repulse_launch(int dim, int blocks, hipStream_t s, int nunits, const in
                         int* queue, const int* seg, const double* X, const double* DP,
                         double repel, double* F, double* H, size_t hs, int* prog, int* err,
                         long long limit) {
-  dispatch_dim(dim, [&](auto Dc) {
+  dispatch_dim_narrow(dim, [&](auto Dc) {
     constexpr int D = decltype(Dc)::value;
     if (repel == 1.0)
       hipLaunchKernelGGL((faml_sym_repulse<D, true>), dim3(blocks), dim3(kSymT), 0, s, nunits,
@@ -1318,7 +1357,7 @@ void sym_repulse_launch(int dim, int blocks, hipStream_t s, int nunits, const in
 // (profiles/r04/c2_sym_blocks.log) -- fewer sweeps in flight wait less on each other.
 int sym_blocks_per_cu(int dim) {
   int occ = 1;
-  dispatch_dim(dim, [&](auto Dc) {
+  dispatch_dim_narrow(dim, [&](auto Dc) {
     constexpr int D = decltype(Dc)::value;
     GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &occ, (const void*)faml_sym_repulse<D, false>, kSymT, 0));
@@ -1414,7 +1453,7 @@ static int faml_plan_create_impl(ge_ctx* ctx, int n, const int* d_ip, const int*
 static void faml_plan_check(ge_ctx* ctx, int n, int m, const int* h_pt_ip, int dim,
                             const ge_fa_params* p, void* out) {
   GE_REQUIRE(ctx && p && out && h_pt_ip, "null argument");
-  GE_REQUIRE(dim >= 1 && dim <= 4, "dimension must be 1..4");
+  GE_REQUIRE(dim >= 1 && dim <= ge::kMaxDim, "dimension must be 1..16");
   GE_REQUIRE(n > 0 && m > 0 && h_pt_ip[0] == 0 && h_pt_ip[m] == n,
              "P_T must have one entry per fine vertex");
 }

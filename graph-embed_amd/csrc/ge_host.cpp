@@ -279,7 +279,8 @@ void embed_impl(ge_ctx* ctx, ge_comm* comm, int levels, const int* a_n, const in
     else faml_host(ctx, n, ip, ix, dx, m, pip, pix, vA, cA, rA, X, d, it, pr);
   };
   GE_REQUIRE(coords_out && a_n && a_off && a_nz_off, "null argument");
-  GE_REQUIRE(levels >= 0 && dim >= 1 && dim <= 4, "bad levels or dimension");
+  GE_REQUIRE(levels >= 0, "bad levels");
+  GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
   for (int l = 0; l < levels; ++l)  // src/embed.cpp:564-570
     GE_REQUIRE(p_rows[l] == a_n[l + 1], "As[l+1].Rows() must equal P_Ts[l].Rows()");
   auto Aip = [&](int l) { return a_ip + a_off[l]; };
@@ -465,7 +466,7 @@ int ge_force_atlas(ge_ctx* ctx, int n, const int* ip, const int* ix, const doubl
                    double* coords, int init_random, int iterations, const ge_fa_params* p) {
   return guarded([&] {
     GE_REQUIRE(ctx && p && (coords || n == 0), "null argument");
-    GE_REQUIRE(dim >= 1 && dim <= 4, "dimension must be 1..4");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
     GE_REQUIRE(iterations >= 0, "negative iteration count");
     ge::check_csr(n, ip, ix, dx);
     ge::DeviceGuard g(ctx);
@@ -480,7 +481,7 @@ int ge_force_atlas_ml(ge_ctx* ctx, int n, const int* ip, const int* ix, const do
   return guarded([&] {
     GE_REQUIRE(ctx && p && pip && pix && vA && cA && rA && (coords || n == 0),
                "null argument");
-    GE_REQUIRE(dim >= 1 && dim <= 4, "dimension must be 1..4");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
     ge::check_csr(n, ip, ix, dx);
     GE_REQUIRE(m >= 0 && pip[0] == 0 && pip[m] == n, "P_T must have one entry per fine vertex");
     if (n == 0) return;

@@ -9,6 +9,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdlib>
+#include <type_traits>
+
 #include "ge_internal.hpp"
 #include "ge_math.hpp"
 
@@ -251,14 +255,54 @@ __device__ __forceinline__ void neg_over(const double (&x)[D], double mag, doubl
   }
 }
 
+// Dimensions.  Every kernel takes D at compile time, 1..kMaxDim (the oracle's
+// bound).  D <= kNarrowMaxDim has every schedule: the one-workgroup kernel, the
+// persistent coarsest-level kernel, the symmetric sweeps, FAST mode and all the
+// lane / row-slot variants.  Above it only the "wide" schedule is compiled: the
+// ordered-pair kernels, the fused step and the one-workgroup kernel's general form
+// in one variant each (REPEL_ONE = false and LINEAR = false, which give the same
+// bits as their specialisations) and two or three group sizes, because
+// per-lane state grows as xi[D] + acc[D] + e[D] and the build as the number of
+// instantiations.  GE_WIDE_MIN_DIM (default kNarrowMaxDim + 1) sends
+// smaller dimensions through the wide schedule too: same results, for comparisons.
+constexpr int kMaxDim = 16;
+constexpr int kNarrowMaxDim = 4;
+
+inline bool wide_dim(int dim) {
+  int lo = kNarrowMaxDim + 1;
+  if (const char* e = std::getenv("GE_WIDE_MIN_DIM")) lo = std::min(lo, std::max(1, std::atoi(e)));
+  return dim >= lo;
+}
+
+// Doubles per LDS member record {x_0..x_{D-1}, deg+1}: 4 up to D = 3 and 8 up to
+// D = 7 (the widths D <= 4 has always had), then D + 1 rounded up to even, so that
+// records stay 16-byte aligned for ds_read_b128.
+constexpr int rec_width(int D) { return D + 1 <= 4 ? 4 : D + 1 <= 8 ? 8 : (D + 2) & ~1; }
+
+// LDS a workgroup may use on gfx950 (160 KiB), less 1 KiB kept for the kernels'
+// small static arrays.
+constexpr size_t kLdsBlock = 160 * 1024 - 1024;
+
+#define GE_DIM_CASE(N) \
+  case N: f(std::integral_constant<int, N>()); break;
+
 template <class F>
 void dispatch_dim(int dim, F&& f) {
   switch (dim) {
-    case 1: f(std::integral_constant<int, 1>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    case 3: f(std::integral_constant<int, 3>()); break;
-    case 4: f(std::integral_constant<int, 4>()); break;
-    default: throw Error(GE_ERR_ARG, "dimension must be 1..4");
+    GE_DIM_CASE(1) GE_DIM_CASE(2) GE_DIM_CASE(3) GE_DIM_CASE(4)
+    GE_DIM_CASE(5) GE_DIM_CASE(6) GE_DIM_CASE(7) GE_DIM_CASE(8)
+    GE_DIM_CASE(9) GE_DIM_CASE(10) GE_DIM_CASE(11) GE_DIM_CASE(12)
+    GE_DIM_CASE(13) GE_DIM_CASE(14) GE_DIM_CASE(15) GE_DIM_CASE(16)
+    default: throw Error(GE_ERR_ARG, "dimension must be 1..16");
+  }
+}
+
+// The schedules compiled for D <= kNarrowMaxDim only (callers check wide_dim first).
+template <class F>
+void dispatch_dim_narrow(int dim, F&& f) {
+  switch (dim) {
+    GE_DIM_CASE(1) GE_DIM_CASE(2) GE_DIM_CASE(3) GE_DIM_CASE(4)
+    default: throw Error(GE_ERR_STATE, "this schedule is built for dimensions 1..4 only");
   }
 }
 

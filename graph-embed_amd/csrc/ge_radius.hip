@@ -242,13 +242,17 @@ __global__ void rescale_kernel(int mc, const int* __restrict__ pip, const int* _
 
 template <class F>
 void with_dim(int dim, F&& f) {
+  // D enters the kernels through dist_dev only (a serial sum of D squares)
+#define GE_RADIUS_DIM(N) \
+  case N: f(std::integral_constant<int, N>()); break;
   switch (dim) {
-    case 1: f(std::integral_constant<int, 1>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    case 3: f(std::integral_constant<int, 3>()); break;
-    case 4: f(std::integral_constant<int, 4>()); break;
-    default: throw Error(GE_ERR_ARG, "dimension must be 1..4");
+    GE_RADIUS_DIM(1) GE_RADIUS_DIM(2) GE_RADIUS_DIM(3) GE_RADIUS_DIM(4)
+    GE_RADIUS_DIM(5) GE_RADIUS_DIM(6) GE_RADIUS_DIM(7) GE_RADIUS_DIM(8)
+    GE_RADIUS_DIM(9) GE_RADIUS_DIM(10) GE_RADIUS_DIM(11) GE_RADIUS_DIM(12)
+    GE_RADIUS_DIM(13) GE_RADIUS_DIM(14) GE_RADIUS_DIM(15) GE_RADIUS_DIM(16)
+    default: throw Error(GE_ERR_ARG, "dimension must be 1..16");
   }
+#undef GE_RADIUS_DIM
 }
 
 }  // namespace
@@ -368,7 +372,8 @@ extern "C" int ge_radius_step_device(ge_ctx* ctx, int m, double* cA, double* rA,
                                      const double* cAc, const double* rAc, const int* AcI,
                                      const int* AcJ, int* used_device) {
   return ge::guarded([&] {
-    GE_REQUIRE(ctx && m >= 0 && cA && rA && dim >= 1 && dim <= 4, "bad radius-step arguments");
+    GE_REQUIRE(ctx && m >= 0 && cA && rA, "bad radius-step arguments");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
     GE_REQUIRE(base || (PIc && PJc && cAc && rAc && AcI && AcJ), "null argument");
     ge::DeviceGuard g(ctx);
     const bool dev = ge::radius_step_device(ctx, m, cA, rA, dim, base != 0, mc, PIc, PJc, cAc,

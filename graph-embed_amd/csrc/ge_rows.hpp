@@ -265,12 +265,15 @@ __device__ __forceinline__ void ordered_edge_sum(int e0, int e1, int lane, doubl
 #ifndef GE_SPLIT_U
 #define GE_SPLIT_U 4
 #endif
-constexpr int kSplitU = GE_SPLIT_U;
-constexpr int kSplitChunk = 192 * kSplitU;  // 3 computing waves x 64 lanes x U
+// Terms per computing lane per chunk.  The two chunk buffers are 2 x 192 U x D doubles
+// and a lane holds U x D terms: U shrinks with D so both stay at the D = 4 size.
+constexpr int split_u(int D) { return D <= 4 ? GE_SPLIT_U : D <= 8 ? 2 : 1; }
+constexpr int split_chunk(int D) { return 192 * split_u(D); }  // 3 computing waves x 64 lanes x U
 
 template <int D, class Term>
 __device__ __forceinline__ void ordered_edge_sum_split(int e0, int e1, int tid, double* buf,
                                                        Term&& term, double (&acc)[D]) {
+  constexpr int kSplitU = split_u(D), kSplitChunk = split_chunk(D);
   const bool summer = tid < 64;
   const int w = tid - 64;  // computing lane 0..191
   // branch-free over the U terms of a lane (indices clamped into the row, the
@@ -377,7 +380,7 @@ __device__ __forceinline__ bool binade_result(long long P0, int uexp, long long 
 // LDS bytes of the classed kernel (heavy / medium rows) and of a tile.
 template <int D, class P>
 struct RowsLds {
-  static constexpr size_t heavy = sizeof(double) * 2 * kSplitChunk * D;
+  static constexpr size_t heavy = sizeof(double) * 2 * split_chunk(D) * D;
   static constexpr size_t medium = sizeof(double) * 4 * 64 * D;
   static constexpr size_t bytes = heavy > medium ? heavy : medium;
   static constexpr size_t tile = sizeof(double) * kTileCap * D +

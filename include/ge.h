@@ -59,6 +59,21 @@ int ge_ctx_destroy(ge_ctx* ctx);
 int ge_ctx_set_stream(ge_ctx* ctx, void* hip_stream);
 int ge_ctx_sync(ge_ctx* ctx);
 
+/* ---- the embedding dimension ----
+ * Every device entry point below that takes `dim` -- ge_force_atlas, ge_fa_plan_*,
+ * ge_force_atlas_ml, ge_faml_plan_*, ge_embed, ge_radius_step_device and their
+ * *_dist / ge_faml_plan_create_shard forms -- accepts 1 <= dim <= 16 (GE_MAX_DIM)
+ * with the same bit-exact STRICT contract; anything else is GE_ERR_ARG with a message
+ * that names the range.  dim <= 4 has every schedule.  dim >= 5 runs the ordered-pair
+ * kernels, the fused per-iteration step (graph replay for long runs) and the
+ * one-workgroup kernel in its general form (up to 256 rows): no persistent
+ * coarsest-level kernel, no symmetric sweeps, and GE_MODE_FAST runs the STRICT
+ * kernels (exact results satisfy its tolerance).
+ * GE_WIDE_MIN_DIM=<d> in the environment sends dim >= d (d <= 4) through that
+ * schedule too: same results, for comparisons.  ge_embed_via_minimization_ml keeps
+ * sending dim > 4 to its host path. */
+#define GE_MAX_DIM 16
+
 /* ---- single-level ForceAtlas ----
  * Replaces partition::forceAtlas(A, dim, coords, iterations, ks, ksmax, repel,
  * attract, gravity, useWeights, linlog, nohubs, delta, tolerate, normalize)
