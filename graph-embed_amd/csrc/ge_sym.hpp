@@ -236,11 +236,31 @@ __device__ __forceinline__ void report_give_up(bool give_up, int lane, int* err)
   if (give_up && lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Hints (see sweep_prio).  The wait also tells the sweep how it stands in its convoy:
+//   spun   the flag was not yet set: the sweep has caught its predecessor;
+//   lead   the predecessor has already handed over the tile kLook tiles further on
+//          (`look`: that tile's counter, clamped by the caller to the aggregate's last
+//          one, where a hit means the predecessor is done: the lead is unbounded).
+// The look-ahead is one more relaxed load, unordered against everything else: it may
+// see the counter before or after the predecessor's store.  Both are HINTS: they feed
+// s_setprio and the stamps and nothing else.  No sum, address or trip count may ever
+// depend on them, so the result cannot; only `flag >= A` orders the hand-over.
+constexpr int kLook = 16;  // 4, 8 and 12 ran 1.0, 0.5 and 0.15 ms per step slower
+
 template <bool STAMP>
-__device__ __forceinline__ long long handover_wait(const int* flag, int A, int* err,
-                                                   long long limit, bool& give_up) {
+__device__ __forceinline__ long long handover_wait(const int* flag, const int* look, int A,
+                                                   int* err, long long limit, bool& give_up,
+                                                   bool& spun, bool& lead) {
+  spun = lead = false;
   if (give_up) return 0;
-  if (seen(flag) >= A) return 0;
+  // both loads are issued before either is waited for
+  const int f0 = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int l0 = __hip_atomic_load(look, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  lead = __builtin_amdgcn_readfirstlane(l0) >= A;
+  if (__builtin_amdgcn_readfirstlane(f0) >= A) return 0;
+  spun = true;
+  // a spinner at a raised priority would take issue slots from the waves it waits for
+  __builtin_amdgcn_s_setprio(0);
   const long long t0 = rt_now();
   for (int k = 1;; ++k) {
     __builtin_amdgcn_s_sleep(1);
@@ -268,6 +288,24 @@ __device__ __forceinline__ void rows_prio(int rem, int quantum) {
   else if (lv == 2) __builtin_amdgcn_s_setprio(2);
   else if (lv == 1) __builtin_amdgcn_s_setprio(1);
   else __builtin_amdgcn_s_setprio(0);
+}
+
+// Issue priority of a sweep for its next column tile, from its slack in the convoy
+// (the hints of handover_wait; wave-uniform, as s_setprio ignores EXEC).  The grid is
+// persistent, so the age order of a SIMD's three waves is fixed for the launch, and at
+// equal priority the oldest issues nearly unimpeded while the youngest gets the
+// leftover slots.  A sweep that runs ahead only catches its predecessor and spins, so a
+// convoy moves at the pace of its slowest member: the priority goes to the sweeps
+// that lag and away from those that just had to wait.
+//   spun     this tile's wait found the flag unset (no slack to lose)     -> 0
+//   lead     the predecessor is kLook tiles further on (this one lags)    -> 2
+//   otherwise                                                             -> 1
+// Row blocks keep rows_prio.  Returns whether the tile runs raised (the stamps' census).
+__device__ __forceinline__ bool sweep_prio(bool spun, bool lead) {
+  if (spun) __builtin_amdgcn_s_setprio(0);
+  else if (lead) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(1);
+  return !spun;
 }
 
 // A row block: the 64 rows of tile A against all s members in ascending order,
@@ -334,15 +372,17 @@ __device__ __forceinline__ void rows_block(int lane, int base, int s, int A, con
 // Per-unit timeline of one launch (STAMP builds only, GE_SYM_STAMPS): 8 words per
 // unit in queue order -- s_memrealtime (100 MHz, one clock for the whole chip)
 // when the wave took the unit, when its first column tile was handed over, when it
-// finished, the ticks spent spinning on hand-overs, HW_ID and XCC_ID.
+// finished, the ticks spent spinning on hand-overs, HW_ID, XCC_ID, the column tiles
+// run at a raised issue priority and the hand-over waits that spun (sweep_prio).
 constexpr int kStampWords = 8;
-
 
 // One symmetric sweep (unit kind 0): row tile A against the columns >= 64A, the
 // column sums handed to the next sweep tile by tile.  rec / col: this wave's rings
-// (see kSymRing).  STAMP: spin ticks and the first hand-over time.
+// (see kSymRing).  STAMP: spin ticks, the first hand-over time and the hints' census
+// (hint[0]: raised tiles, hint[1]: waits that spun).
 template <int D, bool REPEL_ONE, bool STAMP>
 __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int* tprog,
+                                           int (&hint)[2],
                                            const double* __restrict__ X,
                                            const double* __restrict__ DP, double repel,
                                            bool repel_ok, double* __restrict__ F,
@@ -364,10 +404,15 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
   const int ntiles = (ncols + 63) >> 6;
   bool ok_prev = true;
   for (int tt = 0; tt < ntiles; ++tt) {
+    bool spun = false, lead = true;  // sweep 0 has no predecessor: an unbounded lead
     if (A > 0) {  // the sweeps 0..A-1 have written column tile A + tt back
-      const long long w = handover_wait<STAMP>(tprog + tt, A, err, limit, give_up);
+      // the look-ahead is clamped to this aggregate's last counter (tprog[ntiles - 1])
+      const long long w =
+          handover_wait<STAMP>(tprog + tt, tprog + min(tt + kLook, ntiles - 1), A, err, limit,
+                               give_up, spun, lead);
       if (STAMP) {
         spin += w;
+        hint[1] += spun;
         if (tt == 0) t_first = rt_now();
       }
       // the F loads below are agent-scope (served past the L2) and issued only after
@@ -403,6 +448,8 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
       rec[D * kRecSlots + p + kSymRing] = dc;
     }
     wave_lds_sync();
+    const bool raised = sweep_prio(spun, lead);  // for the tile's 64 steps
+    if (STAMP) hint[0] += raised;
     // the steps of tile tt read tiles tt-1 and tt; the diagonal meets steps < 127
     const bool fast = rows_ok && ok_cur && ok_prev;
     const int coff = cb - 64 * tt;
@@ -440,6 +487,7 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
                                    racc);
   if (ntiles >= 2)
     sym_handover<D>(ntiles - 1, lane, A + 1, ncols, cbase, col, cbd - 64, H, hs, tprog);
+  __builtin_amdgcn_s_setprio(0);  // the drain ran at the last tile's level
   // the rows' sums: the caller writes them to F
 #pragma unroll
   for (int k = 0; k < D; ++k) rout[k] = racc[k];
@@ -447,7 +495,8 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
 
 // Stamp record of one unit (STAMP builds): see kStampWords.
 __device__ __forceinline__ void stamp_unit(long long* stamps, int qi, long long t_take,
-                                           long long t_first, long long spin) {
+                                           long long t_first, long long spin,
+                                           const int (&hint)[2]) {
   long long* w = stamps + (size_t)qi * kStampWords;
   w[0] = t_take;
   w[1] = t_first;
@@ -455,6 +504,8 @@ __device__ __forceinline__ void stamp_unit(long long* stamps, int qi, long long 
   w[3] = spin;
   w[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
   w[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
+  w[6] = hint[0];
+  w[7] = hint[1];
 }
 
 // Unit kinds: a symmetric sweep, or a whole row block (an aggregate whose sweep
@@ -502,6 +553,7 @@ faml_sym_repulse(int nunits, const int4* __restrict__ units, int* __restrict__ q
     qi = __builtin_amdgcn_readfirstlane(qi);
     if (qi >= nunits) break;  // every wave leaves once the queue is drained
     long long t_take = 0, t_first = 0, spin = 0;
+    int hint[2] = {0, 0};
     if (STAMP) t_take = t_first = rt_now();
     const int4 u = units[qi];
     const int A = u.y;
@@ -515,15 +567,15 @@ faml_sym_repulse(int nunits, const int4* __restrict__ units, int* __restrict__ q
       rows_block<D, REPEL_ONE>(lane, base, s, A, X, DP, repel, repel_ok, rec, F, u.z);
     } else {  // a sweep
       double racc[D];
-      sweep_unit<D, REPEL_ONE, STAMP>(lane, A, base, s, prog + u.z + A, X, DP, repel,
-                                              repel_ok, F, H, hs, err, limit, give_up, rec, col,
-                                              spin, t_first, racc);
+      sweep_unit<D, REPEL_ONE, STAMP>(lane, A, base, s, prog + u.z + A, hint, X,
+                                      DP, repel, repel_ok, F, H, hs, err, limit, give_up, rec,
+                                      col, spin, t_first, racc);
       if (64 * A + lane < s) {
 #pragma unroll
         for (int k = 0; k < D; ++k) F[(rb + lane) * D + k] = racc[k];
       }
     }
-    if (STAMP && lane == 0) stamp_unit(stamps, qi, t_take, t_first, spin);
+    if (STAMP && lane == 0) stamp_unit(stamps, qi, t_take, t_first, spin, hint);
     wave_lds_sync();
   }
   report_give_up(give_up, lane, err);

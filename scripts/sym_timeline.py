@@ -2,10 +2,12 @@
 
 Builds the C4 level-0 plan as bench.py does, runs ITERS iterations with the
 stamping kernel variant, and summarises the last launch's per-unit stamps
-(ge_sym.hpp: take / first hand-over / end / spin ticks of s_memrealtime, 100 MHz):
+(ge_sym.hpp: take / first hand-over / end / spin ticks of s_memrealtime, 100 MHz,
+HW_ID, XCC_ID, tiles run at raised issue priority, waits that spun):
 launch span, wave occupancy over time, parked share, the tail after the queue
-drained, and the critical aggregates' chains.  With STAMPS_ONLY=path it only
-analyses an existing dump.
+drained, the critical aggregates' chains, spin and busy shares by the wave's slot on
+its SIMD (the age proxy) and the census of the priority hints.  With
+STAMPS_ONLY=path it only analyses an existing dump.
 """
 import json
 import os
@@ -85,6 +87,42 @@ def analyse(path):
     v = np.array(list(per.values())) / span
     out["simds_seen"] = int(len(per))
     out["busy_waves_per_simd"] = {"min": float(v.min()), "median": float(np.median(v)), "max": float(v.max())}
+    # per wave slot of the SIMD (HW_ID bits 3:0).  The grid is resident from dispatch, so
+    # a wave keeps its slot for the whole launch and the slot is the proxy of its age on
+    # the SIMD (equal issue priorities fall back to age).  Shares are of the time the
+    # slot's waves held a unit; tiles = column tiles the slot's sweeps ran.
+    slot = hw & 15
+    rem = np.array([aggs[int(a)][2] for a in units[:, 0]]) - units[:, 1]  # a sweep's column tiles
+    by_slot = {}
+    for s in sorted(set(int(x) for x in slot)):
+        sel = (slot == s) & sw
+        if not sel.any():
+            continue
+        by_slot[str(s)] = {"units": int(sel.sum()), "waves": int(len(set(simd[sel].tolist()))),
+                           "spin_share": float(spin[sel].sum() / dur[sel].sum()),
+                           "busy_share": float(busy[sel].sum() / dur[sel].sum()),
+                           "busy_us_per_tile": float(busy[sel].sum() / max(rem[sel].sum(), 1)),
+                           "held_us_per_tile": float(dur[sel].sum() / max(rem[sel].sum(), 1))}
+    out["by_wave_slot"] = by_slot
+    # words 6 and 7 (ge_sym.hpp kStampWords): tiles run at raised priority, waits that spun.
+    # A wait spins when the sweep has no tile of lead over its predecessor at that flag
+    # check, so spun / tiles per unit is the share of checks with zero lead.
+    # (a library from before these words leaves them unwritten: no census then)
+    if (st.shape[1] >= 8 and sw.any() and (st[:, 6:8] >= 0).all() and (st[sw, 6:8].sum() > 0)
+            and (st[sw, 7] <= rem[sw]).all()):
+        raised, spun = st[sw, 6].astype(float), st[sw, 7].astype(float)
+        tiles = np.maximum(rem[sw], 1).astype(float)
+        q = [0, 10, 25, 50, 75, 90, 100]
+        out["hints"] = {"tiles": int(rem[sw].sum()), "raised_tiles": int(raised.sum()),
+                        "spun_waits": int(spun.sum()),
+                        "spun_share_of_checks": float(spun.sum() / tiles.sum()),
+                        "raised_share_of_tiles": float(raised.sum() / tiles.sum()),
+                        "percentiles": q,
+                        "spun_share_per_unit": [float(x) for x in np.percentile(spun / tiles, q)],
+                        "raised_share_per_unit": [float(x) for x in np.percentile(raised / tiles, q)],
+                        "spun_share_by_slot": {k: float(st[(slot == int(k)) & sw, 7].sum()
+                                                        / max(rem[(slot == int(k)) & sw].sum(), 1))
+                                               for k in by_slot}}
     return out
 
 
