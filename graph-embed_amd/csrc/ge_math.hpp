@@ -25,7 +25,14 @@
 // two Newton steps, multiply, one FMA correction, FMA, v_div_fixup -- is the
 // compiler's own instruction sequence on the same operands, so the bits are the
 // same as `/`.  Outside the domain the kernels use `/`.  ge_selftest_math()
-// checks the identity on the device (tests/test_gpu_parity.py).
+// checks the identity on the device on random operands (tests/test_gpu_parity.py);
+// ge_math_cases() returns the helpers' bits for a caller's operands, and
+// tests/test_gpu_math_exact.py compares them with exact quotients and roots on
+// hard-to-round families (denominators next to a power of two, numerators that put
+// the quotient 2^-106 from a rounding boundary): recip_of + div_by, sqrt_normal and
+// the compiler's own `/` and sqrt are correctly rounded on all of them.  The
+// rcp-free reciprocal of ge_pair.hpp pair_den needs one correction, for
+// denominators whose significand is all ones; see there.
 #pragma once
 
 #include <hip/hip_runtime.h>

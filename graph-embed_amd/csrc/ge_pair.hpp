@@ -76,10 +76,28 @@ __device__ __forceinline__ double attraction_mag(double dis, double a, double di
 // Each y is then within 2^-80 of 1 / d before its last rounding, like recip_of's (its
 // second Newton step starts from ~2^-44), so the two differ only where 1 / d lies
 // within ~2^-80 of a rounding boundary, and a y off by one ulp changes the quotient
-// only where n / d lies within ~2^-106 of one: the same bits as `/` except with
-// probability ~2^-80 per division (ge_selftest.hip compares every term with the
-// rcp path and with `/` on 2^30 draws per test call, tests/test_gpu_parity.py).  Two
-// quarter-rate v_rcp_f64 and two FMAs fewer per pair than rcp-based reciprocals.
+// only where n / d lies within ~2^-106 of one.  For random operands that is a
+// probability of ~2^-80 per division (ge_selftest.hip compares every term with the rcp
+// path and with `/` on 2^30 draws per test call, tests/test_gpu_parity.py); for
+// structured ones it is not: a denominator whose significand is all ones,
+// d = 2^k (2 - 2^-52), has 1 / d = 2^-k-1 (1 + 2^-53 + 2^-106 ...), 2^-106 above the
+// boundary between 2^-k-1 and the double after it.  A Newton step reaches 1 / d from
+// below, so it lands under the boundary and rounds to the power of two, and with
+// that y every numerator that is a power of two gets the quotient one ulp low
+// (n y exact, remainder n 2^-53, an exact tie rounded to even).  This is the known
+// exception of the correction step (Markstein): with y = RN(1 / d) the quotient is
+// correctly rounded for every numerator, and a Newton step yields RN(1 / d) except
+// for this d.  Measured on an MI355X
+// (tests/test_gpu_math_exact.py, exact references from tests/math_cases.py): the
+// uncorrected pair_den missed exactly these, 1 098 of 144 447 directed (s, n, c) cases
+// -- the nine all-ones distances times the 122 power-of-two numerators -- while
+// v_rcp_f64 + two steps (recip_of) and the compiler's `/` and sqrt missed none of
+// 599 375 quotients and 1 612 roots.  Distances of that form are reachable from
+// coordinates (e = (0.5, 0x1.bb67ae8584caap-1) has |e| = 1 - 2^-53).  pair_den
+// therefore sets y to RN(1 / d) when d's significand is all ones (three
+// instructions per pair).  dis^2 cannot take that form (no double's rounded square
+// has an all-ones significand), so 1 / dis^2 needs no such step.  Two quarter-rate
+// v_rcp_f64 and two FMAs fewer per pair than rcp-based reciprocals.
 struct PairDen {
   double dis;
   Recip rdis, rdd;  // {dis, ~1/dis}, {dis * dis, ~1/dis^2}
@@ -101,7 +119,13 @@ __device__ __forceinline__ PairDen pair_den(double s) {
   const double dd = dis * dis;
   const double z0 = yd * yd;
   const double ydd = __builtin_fma(z0, __builtin_fma(-dd, z0, 1.0), z0);
-  return PairDen{dis, Recip{dis, yd}, Recip{dd, ydd}};
+  // The structured exception (header comment): dis = 2^k (2 - 2^-52), significand all
+  // ones.  Its reciprocal 2^-k-1 (1 + 2^-53 + 2^-106 ...) lies 2^-106 above a rounding
+  // boundary and the Newton step arrives from below, so yd came out as the power of two
+  // 2^-k-1 where RN(1 / dis) is the double above it: low word 1, high word as computed.
+  const bool ones = __builtin_amdgcn_frexp_mant(dis) == 0x1.fffffffffffffp-1;
+  const double yr = __hiloint2double(__double2hiint(yd), ones ? 1 : __double2loint(yd));
+  return PairDen{dis, Recip{dis, yr}, Recip{dd, ydd}};
 }
 
 // Repulsion of j on i (:152-166): the term added to row i's sum, out[k] =

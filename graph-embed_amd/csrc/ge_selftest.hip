@@ -2,7 +2,8 @@
 // (ge_math.hpp): for operands in the domain the strict kernels admit, div_by
 // must return the same bits as the compiler's IEEE `/`; and the repulsion term
 // with pair_den's rcp-free reciprocals (ge_pair.hpp) the same bits as with
-// recip_of's and as the `/` form.
+// recip_of's and as the `/` form.  ge_math_cases runs the same helpers on operands
+// the caller chooses and returns the bits (tests/test_gpu_math_exact.py).
 
 #include <hip/hip_runtime.h>
 
@@ -121,8 +122,88 @@ __global__ void selftest_kernel(long long samples, unsigned long long seed,
   if (fails) atomicAdd(bad, fails);
 }
 
+__device__ __forceinline__ unsigned long long raw(double v) {
+  return (unsigned long long)__double_as_longlong(v);
+}
+
+template <int D>
+__device__ __forceinline__ void rep_case(const double* __restrict__ row,
+                                         unsigned long long* __restrict__ out) {
+  double xi[D], ta[D], tb[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) xi[k] = row[k];
+  rep_term<D, true, false>(xi, row + D, row[2 * D], row[2 * D + 1], row[2 * D + 2], ta);
+  rep_term<D, false, false>(xi, row + D, row[2 * D], row[2 * D + 1], row[2 * D + 2], tb);
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    out[k] = raw(ta[k]);
+    out[D + k] = raw(tb[k]);
+  }
+}
+
+// One thread per case: the caller's operands through the production helpers, the
+// raw bits of every result back (ge.h ge_math_cases has the row layouts).
+__global__ void math_cases_kernel(int op, int dim, long long count, int win, int wout,
+                                  const double* __restrict__ in,
+                                  unsigned long long* __restrict__ out) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const double* a = in + t * win;
+  unsigned long long* o = out + t * wout;
+  switch (op) {
+    case GE_MATH_SQRT:
+      o[0] = raw(sqrt_normal(a[0]));
+      o[1] = raw(sqrt(a[0]));
+      break;
+    case GE_MATH_DIV:
+      o[0] = raw(div_by(a[0], a[1], recip_of(a[1])));
+      o[1] = raw(a[0] / a[1]);
+      break;
+    case GE_MATH_PAIR: {
+      const PairDen pd = pair_den(a[0]);
+      o[0] = raw(pd.dis);
+      o[1] = raw(div_by_nz(a[1], pd.rdis));
+      o[2] = raw(div_by_nz(a[2], pd.rdd));
+      o[3] = raw(a[1] / pd.dis);
+      o[4] = raw(a[2] / (pd.dis * pd.dis));
+      break;
+    }
+    default:  // GE_MATH_REP
+      switch (dim) {
+        case 1: rep_case<1>(a, o); break;
+        case 2: rep_case<2>(a, o); break;
+        case 3: rep_case<3>(a, o); break;
+        default: rep_case<4>(a, o); break;
+      }
+  }
+}
+
 }  // namespace
 }  // namespace ge
+
+extern "C" int ge_math_cases(ge_ctx* ctx, int op, int dim, long long count, const double* in,
+                             unsigned long long* out) {
+  return ge::guarded([&] {
+    GE_REQUIRE(ctx && count >= 0 && (count == 0 || (in && out)), "bad arguments");
+    GE_REQUIRE(op >= GE_MATH_SQRT && op <= GE_MATH_REP, "unknown op");
+    GE_REQUIRE(op != GE_MATH_REP || (dim >= 1 && dim <= 4), "rep: dimension must be 1..4");
+    if (count == 0) return;
+    const int win = op == GE_MATH_SQRT ? 1 : op == GE_MATH_DIV ? 2 : op == GE_MATH_PAIR ? 3
+                                                                                       : 2 * dim + 3;
+    const int wout = op == GE_MATH_PAIR ? 5 : op == GE_MATH_REP ? 2 * dim : 2;
+    ge::DeviceGuard g(ctx);
+    ge::DevBuf<double> d_in((size_t)count * win);
+    ge::DevBuf<unsigned long long> d_out((size_t)count * wout);
+    d_in.upload(in, (size_t)count * win, ctx->stream);
+    const long long blocks = (count + 255) / 256;
+    GE_REQUIRE(blocks <= 0x7fffffffLL, "too many cases");
+    hipLaunchKernelGGL(ge::math_cases_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, op,
+                       dim, count, win, wout, d_in.p, d_out.p);
+    GE_HIP(hipGetLastError());
+    d_out.download(out, (size_t)count * wout, ctx->stream);
+    GE_HIP(hipStreamSynchronize(ctx->stream));
+  });
+}
 
 extern "C" int ge_selftest_math(ge_ctx* ctx, long long samples, unsigned long long seed,
                                 long long* mismatches) {

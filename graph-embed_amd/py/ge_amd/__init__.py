@@ -30,6 +30,7 @@ HEADER = os.path.join(REPO_ROOT, "include", "ge.h")
 
 MODE_STRICT = 0
 MODE_FAST = 1
+MATH_OPS = {"sqrt": 0, "div": 1, "pair": 2, "rep": 3}  # GE_MATH_*
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -129,6 +130,9 @@ _SIGS = {
     "ge_faml_plan_destroy": (ctypes.c_int, [_vp]),
     "ge_selftest_math": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_ulonglong,
                                         ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_math_cases": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _f64p,
+                                     np.ctypeslib.ndpointer(dtype=np.uint64,
+                                                            flags="C_CONTIGUOUS")]),
     "ge_rmat_csr": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong,
                                    ctypes.POINTER(_vp)]),
     "ge_largest_component": (ctypes.c_int, [ctypes.c_int, _i32p, _i32p, _f64p,
@@ -375,6 +379,22 @@ class Context:
         bad = ctypes.c_longlong()
         _check(lib().ge_selftest_math(self.h, samples, seed, ctypes.byref(bad)))
         return bad.value
+
+    def math_cases(self, op, rows, dim=0):
+        """ge_math_cases: the production helpers on the caller's operands.  op: "sqrt",
+        "div", "pair" or "rep"; rows: one case per row (include/ge.h has the columns).
+        Returns the raw result bits, one uint64 row per case."""
+        code = MATH_OPS[op]
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        rows = rows.reshape(len(rows), -1)
+        win = {"sqrt": 1, "div": 2, "pair": 3, "rep": 2 * dim + 3}[op]
+        wout = {"sqrt": 2, "div": 2, "pair": 5, "rep": 2 * dim}[op]
+        if rows.shape[1] != win:
+            raise ValueError(f"{op}: {win} operands per case, got {rows.shape[1]}")
+        out = np.zeros((len(rows), wout), dtype=np.uint64)
+        _check(lib().ge_math_cases(self.h, code, dim, len(rows), rows.reshape(-1),
+                                   out.reshape(-1)))
+        return out
 
     def fa_plan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw):
         return FaPlan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw)

@@ -418,6 +418,23 @@ int ge_uniform_stream(unsigned seed, long long count, double* out);
 int ge_selftest_math(ge_ctx* ctx, long long samples, unsigned long long seed,
                      long long* mismatches);
 
+/* Diagnostics: the production helpers of the strict kernels on the caller's own
+ * operands, one device thread per case, raw result bits back -- so that a test can
+ * compare them with a correctly rounded reference and name a failing operand.  `in`
+ * holds `count` rows of doubles, `out` receives `count` rows of bit patterns:
+ *   GE_MATH_SQRT  in  s                     out sqrt_normal(s), the compiler's sqrt(s)
+ *   GE_MATH_DIV   in  n, d                  out div_by(n, d, recip_of(d)), n / d
+ *   GE_MATH_PAIR  in  s, n, c               out pair_den(s): dis, div_by_nz(n, rdis),
+ *                                               div_by_nz(c, rdd), n / dis, c / (dis * dis)
+ *   GE_MATH_REP   in  x_i[dim], x_j[dim],   out rep_term<dim, true, false>[dim],
+ *                     deg_i + 1, deg_j + 1,     rep_term<dim, false, false>[dim]
+ *                     repel                     (dim = 1..4; ignored by the other ops)
+ * (graph-embed_amd/csrc/ge_math.hpp, ge_pair.hpp).  The operands are used as given:
+ * the domain checks of the kernels (coord_ok, weight_ok) are the caller's. */
+enum { GE_MATH_SQRT = 0, GE_MATH_DIV = 1, GE_MATH_PAIR = 2, GE_MATH_REP = 3 };
+int ge_math_cases(ge_ctx* ctx, int op, int dim, long long count, const double* in,
+                  unsigned long long* out);
+
 /* ---- synthetic inputs (bench / tests) ----
  * Graph500 R-MAT (0.57, 0.19, 0.19, 0.05) with a counter-based SplitMix64
  * generator (definition: tests/graphs.py), symmetrised, deduplicated, unit
