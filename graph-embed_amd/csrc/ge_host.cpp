@@ -551,6 +551,13 @@ int ge_hier_info(const ge_hier* h, int* path, int* rounds, long long rebuilt[3])
   });
 }
 
+int ge_hier_census(const ge_hier* h, ge_partition_census* out) {
+  return guarded([&] {
+    GE_REQUIRE(h && out, "null argument");
+    *out = h->census;
+  });
+}
+
 int ge_hier_final_graph(const ge_hier* h, ge_csr** adj) {
   return guarded([&] {
     GE_REQUIRE(h && adj, "null argument");

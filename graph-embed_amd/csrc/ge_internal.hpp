@@ -139,6 +139,7 @@ struct ge_hier {
   // with: the alive vertices' adjacency and alpha by `used` slot
   int path = GE_PARTITION_PATH_HOST, rounds = 0;
   long long rebuilt[3] = {0, 0, 0};
+  ge_partition_census census{};  // all zeros unless GE_PARTITION_CENSUS=1 (device paths)
   ge_csr final_adj;
   std::vector<double> final_alpha;
 };

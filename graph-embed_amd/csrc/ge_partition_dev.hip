@@ -107,7 +107,12 @@ enum {
   // here for the profile
   C_SH_SMALL, C_SH_MID, C_SH_BIG, C_SH_PROP, C_SH_CAND, C_SH_HUGE,
   C_SH_DIRTY, C_SH_W, C_SH_B, C_SH_G,
-  C_R_CHG, C_R_BOUND, C_R_PASS,  // rescans of lists > kSmallLen by reason (profile)
+  C_R_CHG, C_R_BOUND, C_R_PASS,  // rescans of lists > kSmallLen by reason (profile, census)
+  // the census (GE_PARTITION_CENSUS, ge_hier_census): sums over rounds and passes
+  C_Z_SMALL, C_Z_MID, C_Z_BIG, C_Z_HUGE,  // lists scanned per class
+  C_K_BOUND, C_K_RUNNER, C_K_NONPOS,      // results kept by a recorded bound (classify_scan)
+  C_M_GLOBAL, C_M_LDS, C_M_MAXCAND,       // resolve_block: rounds per phase, largest input
+  C_RB_INPLACE, C_RB_MOVED,               // rebuild_list: written in place / to fresh pool space
   NCNT
 };
 
@@ -181,7 +186,8 @@ struct Dev {
   // global tables
   unsigned long long* okey;
   double* gw1;
-  int prof;     // GE_PROFILE_PARTITION: count rescans by reason
+  int prof;     // GE_PROFILE_PARTITION or the census: count rescans by reason
+  int census;   // GE_PARTITION_CENSUS: fill the C_Z_* .. C_RB_* counters
 };
 
 __device__ inline int lane_id() { return threadIdx.x & 63; }
@@ -327,8 +333,13 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
   if (pass == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
     // the previous contraction's counters (every reader has run) and the merge count
     for (int q = 0; q < 4; ++q) {
-      d.cnt[C_SH_DIRTY + q] = d.cnt[C_DIRTY + q];  // DIRTY W B G
-      d.cnt[C_DIRTY + q] = 0;
+      // DIRTY W B G, taken with an exchange: the value comes back from the same
+      // operation that zeroes the slot.  A plain load followed by a plain store of 0
+      // compiled to a scalar load of the four counts and a vector store to C_G issued
+      // before the wait for that load (nothing orders the two memory paths), so C_G
+      // could read as 0
+      const int v = atomicExch(&d.cnt[C_DIRTY + q], 0);
+      atomicExch(&d.cnt[C_SH_DIRTY + q], v);
     }
     *d.gtop = 0;
     d.cnt[C_MERGE] = 0;
@@ -339,7 +350,7 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
     const int x = blockIdx.x * blockDim.x + threadIdx.x + r * stride;
     int u = 0;
     bool resc = false, keepprop = false;
-    int len = 0, why = 0;
+    int len = 0, why = 0, kept = 0;
     if (x < L) {
       u = d.alist[x];
       if (d.alive[u]) {
@@ -365,6 +376,7 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
                 d.arg[u] = a0;
                 d.late[u] = 0;
                 skip = true;
+                kept = 1;
               }
             }
             resc = !skip;
@@ -384,6 +396,7 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
               d.arg[u] = k2;
               d.late[u] = 1;
               resc = false;
+              kept = 2;
             }
           }
           if (resc && d.incremental && last && d.positive && a >= 0 && a == d.t2arg[u] &&
@@ -398,6 +411,7 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
             d.arg[u] = -1;
             d.late[u] = 1;
             resc = false;
+            kept = 3;
           }
         } else {
           resc = d.best[u] == -INFINITY;
@@ -415,6 +429,13 @@ __global__ void classify_scan_kernel(Dev d, int pass, int L, int round, int full
       for (int q = 1; q <= 3; ++q) {
         const unsigned long long m = __ballot(resc && len > kSmallLen && why == q);
         if (lane_id() == 0 && m) atomicAdd(&d.cnt[C_R_CHG + q - 1], __popcll(m));
+      }
+    }
+    if (d.census) {
+#pragma unroll
+      for (int q = 1; q <= 3; ++q) {
+        const unsigned long long m = __ballot(kept == q);
+        if (lane_id() == 0 && m) atomicAdd(&d.cnt[C_K_BOUND + q - 1], __popcll(m));
       }
     }
   }
@@ -774,9 +795,19 @@ __global__ void __launch_bounds__(1024) resolve_kernel(Dev d, int pass, int cidx
   resolve_block(d, pass, cidx);
   __syncthreads();
   if (threadIdx.x == 0) {
+    // (vector loads, which stay ordered with the stores of 0 to the same slots
+    // below: see the hand-over in classify_scan_kernel)
     const int from[6] = {C_SMALL, C_MID, C_BIG, C_PROP, C_CAND, C_HUGE};
+    int v[6];
+    for (int q = 0; q < 6; ++q) v[q] = agent_load(&d.cnt[from[q]]);
+    if (d.census) {  // (the mid list also holds the lists it hands on to big and huge)
+      d.cnt[C_Z_SMALL] += v[0];
+      d.cnt[C_Z_MID] += v[1] - v[2] - v[5];
+      d.cnt[C_Z_BIG] += v[2];
+      d.cnt[C_Z_HUGE] += v[5];
+    }
     for (int q = 0; q < 6; ++q) {
-      d.cnt[C_SH_SMALL + q] = d.cnt[from[q]];
+      d.cnt[C_SH_SMALL + q] = v[q];
       d.cnt[from[q]] = 0;
     }
     d.cnt[C_CAND2] = 0;
@@ -837,6 +868,10 @@ __device__ void resolve_block(Dev d, int pass, int cidx) {
     nxt = t;
     __syncthreads();
   }
+  if (d.census && tid == 0) {  // (one block: plain updates)
+    d.cnt[C_M_GLOBAL] += iters;
+    d.cnt[C_M_MAXCAND] = max(d.cnt[C_M_MAXCAND], d.cnt[cidx]);
+  }
   if (n == 0) return;
   // ---- LDS phase
   for (int s = tid; s < kLocalSlots; s += nt) {
@@ -891,6 +926,7 @@ __device__ void resolve_block(Dev d, int pass, int cidx) {
     __syncthreads();
     n = s_live;
     b ^= 1;
+    if (d.census && tid == 0) d.cnt[C_M_LDS] += 1;
     __syncthreads();
   }
 }
@@ -1077,7 +1113,10 @@ __device__ void rebuild_list(const Dev& d, int u, Key* tk, W* tw, W* tw1, int ma
       } else {
         d.aoff[u] = dst;
         d.acap[u] = cap;
+        if (d.census) atomicAdd(&d.cnt[C_RB_MOVED], 1);
       }
+    } else if (d.census) {
+      atomicAdd(&d.cnt[C_RB_INPLACE], 1);
     }
     *s_dst = dst;
     *s_cnt = 0;
@@ -1631,7 +1670,13 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
   d.t2w2 = t2w2.p;
   d.t2b3 = t2b3.p;
   d.patch = std::getenv("GE_PARTITION_NO_PATCH") == nullptr;
-  d.prof = prof ? 1 : 0;
+  // GE_PARTITION_CENSUS=1: which kernel class handled what, for the tests
+  // (ge_hier_census).  Device counters only, exported with the round's counts: no
+  // synchronisation, copy or output of its own.
+  const char* census_env = std::getenv("GE_PARTITION_CENSUS");
+  const bool census = census_env && census_env[0] == '1';
+  d.census = census ? 1 : 0;
+  d.prof = (prof || census) ? 1 : 0;
 
   note("buffers allocated");
   GE_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * NCNT, st));
@@ -1783,7 +1828,18 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
   const int spec = std::min(kSpecMerges, n / 2 + 1);
   double t_dev = 0, t_host = 0, t_compact = 0;
   long long total_merges = 0;
-  int rounds = 0, compactions = 0;
+  int rounds = 0, compactions = 0, alive_compactions = 0, refetches = 0;
+  // The census: the device counters are 32-bit and only ever grow, so each round's
+  // export is folded into 64-bit host sums by its difference to the last export
+  // (exact while one round adds less than 2^32 to a counter).
+  long long csum[NCNT] = {0};
+  unsigned cprev[NCNT] = {0};
+  auto census_fold = [&](const int* now) {
+    for (int c = C_PATCH; c < NCNT; ++c) {
+      csum[c] += (unsigned)now[c] - cprev[c];
+      cprev[c] = (unsigned)now[c];
+    }
+  };
   std::vector<MergeRec> order;
   std::vector<int> stamp(n, 0), moved(n / 2 + 1);
   auto t_last_note = now();
@@ -1863,6 +1919,7 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     }
     if (rounds <= 2) note("round: matching passes done");
     rb.merges = h_cnt[C_MERGE];
+    if (census) census_fold(h_cnt);
     for (int q = 0; q < 3; ++q) h->rebuilt[q] += h_cnt[C_SH_W + q];  // the previous contraction
     if (prof) {
       for (int q = 0; q < 4; ++q) {  // previous round's contraction (DIRTY W B G)
@@ -1882,6 +1939,7 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     const int nm = rb.merges;
     if (nm > 0) {
       if (nm > spec) {
+        ++refetches;
         GE_HIP(hipMemcpyAsync(h_mrec + spec, mrec.p + spec, sizeof(MergeRec) * (nm - spec),
                               hipMemcpyDeviceToHost, st));
         GE_HIP(hipStreamSynchronize(st));
@@ -1950,6 +2008,7 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
         GE_HIP(hipGetLastError());
         std::swap(d.alist, d.alist2);
         alist_len = M;
+        ++alive_compactions;
       }
       launch_scans(0, rounds + 1);  // the next round's first scans (no rank reads)
       GE_HIP(hipGetLastError());
@@ -2020,6 +2079,35 @@ ge_hier* partition_device(ge_ctx* ctx, int n, const int* I, const int* J, const 
     GE_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < 3; ++q) h->rebuilt[q] += last[C_W + q];
     h->rebuilt[2] -= last[C_PATCH];
+    if (census) {
+      ge_partition_census& c = h->census;
+      census_fold(last);
+      c.scan_small = csum[C_Z_SMALL];
+      c.scan_mid = csum[C_Z_MID];
+      c.scan_big = csum[C_Z_BIG];
+      c.scan_huge = csum[C_Z_HUGE];
+      c.kept_bound = csum[C_K_BOUND];
+      c.kept_runner_up = csum[C_K_RUNNER];
+      c.kept_nonpositive = csum[C_K_NONPOS];
+      c.rescan_changed = csum[C_R_CHG];
+      c.rescan_bound = csum[C_R_BOUND];
+      c.rescan_touched = csum[C_R_PASS];
+      c.match_global_rounds = csum[C_M_GLOBAL];
+      c.match_lds_rounds = csum[C_M_LDS];
+      c.match_max_candidates = last[C_M_MAXCAND];  // a maximum: never wraps
+      c.rebuilt_wave = h->rebuilt[0];
+      c.rebuilt_block = h->rebuilt[1];
+      c.rebuilt_global = h->rebuilt[2];
+      c.rebuilt_in_place = csum[C_RB_INPLACE];
+      c.rebuilt_moved = csum[C_RB_MOVED];
+      c.patched = csum[C_PATCH];
+      c.patch_short = csum[C_PF_SHORT];
+      c.patch_size = csum[C_PF_SIZE];
+      c.patch_fit = csum[C_PF_FIT];
+      c.record_refetches = refetches;
+      c.pool_compactions = compactions;
+      c.alive_compactions = alive_compactions;
+    }
   }
   h->path = ordered ? GE_PARTITION_PATH_DEVICE_ORDERED : GE_PARTITION_PATH_DEVICE_EXACT;
   h->rounds = rounds;

@@ -80,6 +80,7 @@ _SIGS = {
                                            ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "ge_hier_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_hier_census": (ctypes.c_int, [_vp, _vp]),
     "ge_hier_final_graph": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
     "ge_hier_final_alpha": (ctypes.c_int, [_vp, _f64p]),
     "ge_hier_levels": (ctypes.c_int, [_vp, _ip]),
@@ -724,6 +725,17 @@ def _take_csr(h):
 PATH_HOST, PATH_DEVICE_EXACT, PATH_DEVICE_ORDERED = 0, 1, 2  # GE_PARTITION_PATH_*
 
 
+# ge_partition_census (include/ge.h), in declaration order
+CENSUS_FIELDS = (
+    "scan_small", "scan_mid", "scan_big", "scan_huge",
+    "kept_bound", "kept_runner_up", "kept_nonpositive",
+    "rescan_changed", "rescan_bound", "rescan_touched",
+    "match_global_rounds", "match_lds_rounds", "match_max_candidates",
+    "rebuilt_wave", "rebuilt_block", "rebuilt_global", "rebuilt_in_place", "rebuilt_moved",
+    "patched", "patch_short", "patch_size", "patch_fit",
+    "record_refetches", "pool_compactions", "alive_compactions")
+
+
 def _take_hier(h, info):
     try:
         lv = ctypes.c_int()
@@ -746,7 +758,10 @@ def _take_hier(h, info):
         final_graph = _take_csr(g)
         alpha = np.empty(len(final_graph[0]) - 1, dtype=np.float64)
         _check(lib().ge_hier_final_alpha(h, alpha))
+        census = (ctypes.c_longlong * len(CENSUS_FIELDS))()
+        _check(lib().ge_hier_census(h, ctypes.cast(census, _vp)))
         return out, {"path": path.value, "rounds": rounds.value, "rebuilt": list(rebuilt),
+                     "census": dict(zip(CENSUS_FIELDS, (int(v) for v in census))),
                      "final_graph": final_graph, "final_alpha": alpha}
     finally:
         lib().ge_hier_free(h)
@@ -759,7 +774,9 @@ def partition(A, coarsening_factor, printing=False, positive_merging=True, stall
     integers by the exact contraction, other reals by the ordered one); without
     one, or for other inputs, by the library's host path.  info=True returns
     (hierarchy, dict): path (PATH_*), rounds, rebuilt (lists rebuilt by the
-    device's wave / block / global kernels) and the quotient graph the round loop
+    device's wave / block / global kernels), census (CENSUS_FIELDS: which kernel
+    class of the device partition handled what; all zeros unless
+    GE_PARTITION_CENSUS=1 is set at the call) and the quotient graph the round loop
     ended with, final_graph (CSR by the last P_T's row numbers) and final_alpha."""
     ip, ix, dx = _csr(A)
     h = _vp()

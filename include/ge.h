@@ -225,6 +225,40 @@ int ge_partition_single(ge_ctx* ctx, int n, const int* indptr, const int* indice
 #define GE_PARTITION_PATH_DEVICE_EXACT 1
 #define GE_PARTITION_PATH_DEVICE_ORDERED 2
 int ge_hier_info(const ge_hier* h, int* path, int* rounds, long long rebuilt[3]);
+/* Which kernel class of the device partition handled what, for tests.  Collected
+ * only when GE_PARTITION_CENSUS=1 is set when ge_partition / ge_partition_single
+ * is called (device counters carried out with each round's export: no extra
+ * synchronisation, copy or output); all zeros otherwise and on the host path.
+ * Every field is a sum over rounds and passes except match_max_candidates; the
+ * 32-bit device counters are folded into these 64-bit sums at every round's
+ * export, so a sum is exact while one round adds less than 2^32 to it. */
+typedef struct ge_partition_census {
+  /* lists scanned: one thread (<= 16 entries), one wave (<= 512), one block
+   * (<= 16 384), 64 chunk blocks and a combining wave (longer) */
+  long long scan_small, scan_mid, scan_big, scan_huge;
+  /* vertices that kept a result without a rescan: pass 0 by the bound recorded at
+   * the last pass-0 scan, pass >= 1 by the recorded runner-up, last pass by the
+   * recorded bound being non-positive */
+  long long kept_bound, kept_runner_up, kept_nonpositive;
+  /* rescans of lists longer than 16 entries by reason: list or alpha changed, the
+   * recorded bound failed, the argmax was touched */
+  long long rescan_changed, rescan_bound, rescan_touched;
+  /* the matching's last kernel: locally-dominant rounds on global memory (more
+   * than 1 024 live candidates) and in LDS; the largest candidate count it received */
+  long long match_global_rounds, match_lds_rounds, match_max_candidates;
+  /* lists rebuilt per table class (as ge_hier_info), written back in place or
+   * moved to fresh pool space */
+  long long rebuilt_wave, rebuilt_block, rebuilt_global;
+  long long rebuilt_in_place, rebuilt_moved;
+  /* hub lists (longer than 2 048) patched in place; global-class lists rebuilt
+   * instead because the list is short, a set is too small (more than 1 024
+   * absorbed neighbours or partner entries) or the result does not fit */
+  long long patched, patch_short, patch_size, patch_fit;
+  /* rounds whose merges exceeded the 4 096 records exported with the counts;
+   * compactions of the list pool and of the alive list */
+  long long record_refetches, pool_compactions, alive_compactions;
+} ge_partition_census;
+int ge_hier_census(const ge_hier* h, ge_partition_census* out);
 /* What the round loop ended with: the adjacency a[i][k] of the vertices alive at
  * loop exit (rows and columns numbered by `used` slot = the last P_T's row
  * number, columns ascending; free with ge_csr_free) and their alpha (one per row

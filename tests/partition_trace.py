@@ -11,6 +11,9 @@ returns to the oracle's.
 
 reverse=True processes the contraction's merges in reverse: the same terms in a
 wrong grouping.  It exists only to show that a test can see the summation order.
+tie_last=True lets the scan take the last of several maximal neighbours (`>=`):
+a wrong index tie-break, to show that a test can see the right one.  log, a list,
+receives each round's merges as (keeper, absorbed) pairs in `merged` order.
 """
 import numpy as np
 
@@ -34,7 +37,7 @@ def _interpolation(num_cols, sets):
 
 
 def trace(A, cf=None, num_parts=None, positive_merging=True, stall=1.0, matching=2,
-          reverse=False):
+          reverse=False, tie_last=False, log=None):
     """cf: the hierarchy overload; num_parts: the numParts overload; neither: the
     single-P_T overload.  Returns (levels, final_graph, final_alpha): levels as
     (indptr, indices, rows, cols); final_graph the CSR of a[i][k] over the alive
@@ -90,7 +93,7 @@ def trace(A, cf=None, num_parts=None, positive_merging=True, stall=1.0, matching
                     for j in sorted(a[i]):
                         if not notouch[j]:
                             eta = 2 * (a[i][j] / T - ai * alpha[j])
-                            if eta > best:
+                            if eta > best or (tie_last and eta >= best):
                                 best, arg = eta, j
                     max_eta[i], max_ind[i] = best, arg
             for i in used:
@@ -101,6 +104,8 @@ def trace(A, cf=None, num_parts=None, positive_merging=True, stall=1.0, matching
                     if not positive_merging or max_eta[i] > 0:
                         merged.append((j, i) if len(a[i]) < len(a[j]) else (i, j))
                         notouch[i] = notouch[j] = True
+        if log is not None:
+            log.append(list(merged))
         for ip_, jp in (reversed(merged) if reverse else merged):
             for k in sorted(a[jp]):
                 a_jk = a[jp][k]
