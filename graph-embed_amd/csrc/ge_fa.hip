@@ -51,7 +51,6 @@
 namespace ge {
 namespace {
 
-constexpr double kEps = kFaEps;
 FaConst make_const(const ge_fa_params& p) { return make_fa_const(p); }
 
 // deg[i] + 1 with deg the serial row sum of include/forceatlas.hpp:127-140.
@@ -229,8 +228,8 @@ fa_repulse_strict(int n, int rb, int re, int per_block, const double* __restrict
 // ---------------------------------------------------------------------------
 // FAST repulsion: (row block) x (j block) tiles; each block writes a partial
 // sum for its rows into Fpart[jb][row]; fa_reduce_parts sums the partials.
-// Pair term in closed form: F_i += c_ij * (x_i - x_j) / dis^3, dis from one
-// rsqrt + one Newton step, FMA everywhere.
+// Pair term in closed form (fast_rep_pair, ge_pair.hpp): F_i += c_ij * (x_i - x_j) /
+// dis^3, 1 / dis from one rsqrt + two Newton steps, FMA everywhere.
 
 constexpr int kFastJBlocks = 16;  // j-range split
 
@@ -250,7 +249,6 @@ fa_repulse_fast(int n, int rb, int re, const double* __restrict__ X,
   const int jchunk = (n + jblocks - 1) / jblocks;
   const int jbeg = jb * jchunk;
   const int jend = min(n, jbeg + jchunk);
-  const double inv_eps = 1.0 / kEps;
 
   double xi[R][D], di[R], acc[R][D];
 #pragma unroll
@@ -280,24 +278,7 @@ fa_repulse_fast(int n, int rb, int re, const double* __restrict__ X,
       for (int k = 0; k < D; ++k) xj[k] = tile[jj * W + k];
       const double dj = tile[jj * W + D];
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        double e[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) e[k] = xi[r][k] - xj[k];
-        double s = e[0] * e[0];
-#pragma unroll
-        for (int k = 1; k < D; ++k) s = fma(e[k], e[k], s);
-        // y = 1/max(sqrt(s), eps): hardware estimate + two Newton steps.
-        // s == 0 gives inf -> NaN after Newton -> fmin picks 1/eps.
-        double y = __builtin_amdgcn_rsq(s);
-        const double hs = 0.5 * s;
-        y = y * fma(-hs * y, y, 1.5);
-        y = y * fma(-hs * y, y, 1.5);
-        y = fmin(y, inv_eps);
-        const double w = di[r] * dj * (y * y * y);
-#pragma unroll
-        for (int k = 0; k < D; ++k) acc[r][k] = fma(e[k], w, acc[r][k]);
-      }
+      for (int r = 0; r < R; ++r) fast_rep_pair<D>(xi[r], xj, di[r], dj, acc[r]);  // ge_pair.hpp
     }
   }
 #pragma unroll

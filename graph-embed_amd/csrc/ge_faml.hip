@@ -495,6 +495,117 @@ faml_big_repulse(int nitems, const int2* __restrict__ items, int* __restrict__ q
   }
 }
 
+// ---------------------------------------------------------------------------
+// FAST mode (GE_MODE_FAST, D <= 4): the streamed aggregates' repulsion in closed
+// form (fast_rep_pair, ge_pair.hpp), every ordered pair, no ordering between waves.
+// Work items are (aggregate, rows [r0, r1)) with r1 - r0 <= 64 R, taken from the
+// queue by wave; a lane owns up to R rows (r0 + lane + 64 r) in registers and runs
+// over ALL members of the aggregate in P_T order, 64-record tiles through the
+// wave's LDS slice (the next tile's record is loaded into registers while the
+// current one is evaluated).  A row's sum is one lane's fma chain over j = 0 .. s - 1,
+// so its bits do not depend on the item list: a whole plan, a subset plan and a shard
+// plan's local tiles of a split aggregate give the same sums.
+//
+// R = 4 (kFastR): the partner record (D + 1 doubles, one broadcast ds_read per two)
+// is read once for four rows, and four independent chains per lane cover the
+// quarter-rate v_rsq_f64 and the Newton steps' dependent FMAs without a second wave.
+// Per lane 4 x (xi[D] + acc[D] + dir), the record and its prefetched successor, and
+// e / s / y / w of the pairs in flight: 86 / 124 / 122 VGPRs at D = 1 / 2 / 3, inside
+// the 128 of four waves per SIMD, and 168 at D = 4 (three waves; held to 128 it spills
+// 34 registers), no scratch anywhere.  The plan launches as many blocks per CU as
+// fit, at most four.  Inner loop at D = 3: 21 VALU + one v_rsq_f64 per ordered pair,
+// two ds_read_b128 per partner for its four rows (FAST mode).
+// The last item of a row range may use fewer than R row slots (nr, wave-uniform): its
+// partner loop is instantiated per nr, so no slot past r1 is evaluated.
+
+constexpr int kFastR = 4;
+
+template <int D, int R, int NR>
+__device__ __forceinline__ void fast_rows(const double* __restrict__ tile, int cnt,
+                                          const double (&xi)[R][D], const double (&di)[R],
+                                          double (&acc)[R][D]) {
+  constexpr int WV = W<D>::v;
+  for (int jj = 0; jj < cnt; ++jj) {
+    double xj[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) xj[k] = tile[jj * WV + k];
+    const double dj = tile[jj * WV + D];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) fast_rep_pair<D>(xi[r], xj, di[r], dj, acc[r]);
+  }
+}
+
+template <int D, int R>
+__global__ void __launch_bounds__(kHT, D <= 3 ? 4 : 3)
+faml_fast_repulse(int nitems, const int4* __restrict__ items, int* __restrict__ queue,
+                  const int* __restrict__ pt_ip, const double* __restrict__ Xp,
+                  const double* __restrict__ DP, double repel, double* __restrict__ Fscr) {
+  static_assert(R >= 1 && R <= 4, "the partner loop is instantiated for 1..4 row slots");
+  constexpr int WV = W<D>::v;
+  __shared__ __attribute__((aligned(16))) double tiles[kHT / 64][kBigW * WV];
+  const int lane = threadIdx.x & 63;
+  double* tile = tiles[threadIdx.x >> 6];
+  for (;;) {
+    int q = 0;
+    if (lane == 0) q = atomicAdd(queue, 1);
+    q = __builtin_amdgcn_readfirstlane(q);
+    if (q >= nitems) break;  // the queue drain is the kernel's only loop over items
+    const int4 item = items[q];
+    const int base = pt_ip[item.x];
+    const int s = pt_ip[item.x + 1] - base;
+    const int r0 = item.y;
+    const int r1 = min(item.z, s);
+    const int nr = min(R, (r1 - r0 + 63) >> 6);  // wave-uniform
+    double xi[R][D], di[R], acc[R][D];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int li = r0 + lane + 64 * r;
+      const bool ok = li < r1;
+      const size_t c = (size_t)base + (ok ? li : r0);
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        xi[r][k] = ok ? Xp[c * D + k] : 0.0;
+        acc[r][k] = 0.0;
+      }
+      di[r] = ok ? DP[c] * repel : 0.0;
+    }
+    double nx[D + 1];  // this lane's record of the next tile
+    {
+      const size_t c = (size_t)base + min(lane, s - 1);
+#pragma unroll
+      for (int k = 0; k < D; ++k) nx[k] = Xp[c * D + k];
+      nx[D] = DP[c];
+    }
+    for (int j0 = 0; j0 < s; j0 += kBigW) {
+      const int cnt = min(kBigW, s - j0);
+      wave_lds_sync();  // the previous tile has been read by every lane
+#pragma unroll
+      for (int k = 0; k <= D; ++k) tile[lane * WV + k] = nx[k];
+      wave_lds_sync();
+      if (j0 + kBigW < s) {  // lanes past the end re-read the last member (in bounds, unused)
+        const size_t c = (size_t)base + min(j0 + kBigW + lane, s - 1);
+#pragma unroll
+        for (int k = 0; k < D; ++k) nx[k] = Xp[c * D + k];
+        nx[D] = DP[c];
+      }
+      switch (nr) {
+        case 1: fast_rows<D, R, 1>(tile, cnt, xi, di, acc); break;
+        case 2: fast_rows<D, R, (R >= 2 ? 2 : R)>(tile, cnt, xi, di, acc); break;
+        case 3: fast_rows<D, R, (R >= 3 ? 3 : R)>(tile, cnt, xi, di, acc); break;
+        default: fast_rows<D, R, R>(tile, cnt, xi, di, acc); break;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int li = r0 + lane + 64 * r;
+      if (li < r1) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) Fscr[((size_t)base + li) * D + k] = acc[r][k];
+      }
+    }
+  }
+}
+
 // Per streamed member, after faml_big_repulse: the CSR row (:415-467) added to
 // the repulsion sum in stored order (degree-classed, ge_rows.hpp), gravity
 // (:469-474) and the swing/speed update (:477-530).
@@ -760,6 +871,13 @@ struct ge_faml_plan {
   ge::RowStreams rstreams;
   ge::DevBuf<int2> items;
   int nrows = 0, nitems = 0, R = 1, code = 0, rep_blocks = 0;
+  // FAST mode (faml_fast_repulse): set when the caller asked for GE_MODE_FAST, the plan
+  // has streamed rows and the dimension is not on the wide schedule; then no sweep
+  // units, hand-over buffers or progress counters exist
+  int mode = GE_MODE_STRICT;  // as requested (ge_fa_params.mode)
+  bool fast = false;
+  ge::DevBuf<int4> fitems;  // (aggregate, first row, end row, 0), descending work
+  int nfitems = 0, fast_blocks = 0;
   // symmetric repulsion (ge_sym.hpp): sweep units and per-tile progress counters
   bool sym = false;
   bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
@@ -944,11 +1062,37 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
                    [](const Item& x, const Item& y) { return x.work > y.work; });
   std::vector<int2> items;
   for (const Item& it : its) items.push_back(make_int2(it.a, it.r0));
+  // FAST mode: row items of up to kFastR 64-row tiles, whole aggregates and this rank's
+  // tiles of the split ones alike (a row's sum does not depend on the item it is in);
+  // the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) do not apply
+  std::vector<int4> fitems;
+  if (pl->mode == GE_MODE_FAST && !wide) {
+    struct FItem { int a, r0, r1; double work; };
+    std::vector<FItem> fi;
+    auto cut = [&](int a, int b0, int b1) {  // rows [b0, b1) of aggregate a
+      const int s = h_pt_ip[a + 1] - h_pt_ip[a];
+      for (int r0 = b0; r0 < b1; r0 += 64 * kFastR) {
+        const int r1 = std::min(b1, r0 + 64 * kFastR);
+        fi.push_back({a, r0, r1, (double)((r1 - r0 + 63) / 64) * s});
+      }
+    };
+    for (int a : big) cut(a, 0, h_pt_ip[a + 1] - h_pt_ip[a]);
+    for (int a : split) {
+      int t0, t1;
+      tiles_of(a, rank, t0, t1);
+      cut(a, 64 * t0, std::min(h_pt_ip[a + 1] - h_pt_ip[a], 64 * t1));
+    }
+    std::stable_sort(fi.begin(), fi.end(),
+                     [](const FItem& x, const FItem& y) { return x.work > y.work; });
+    for (const FItem& f : fi) fitems.push_back(make_int4(f.a, f.r0, f.r1, 0));
+  }
+  pl->fast = !fitems.empty();
+  pl->nfitems = (int)fitems.size();
   // symmetric sweeps: one unit per (aggregate, row tile), in the order of their
   // earliest start (2A tile-times into the aggregate), larger aggregates first
   {
     const char* e = std::getenv("GE_FAML_SYM");
-    pl->sym = !(e && *e == '0') && !wide;
+    pl->sym = !(e && *e == '0') && !wide && !pl->fast;
   }
   if (pl->sym && (!big.empty() || !split.empty())) {
     // The sweeps of an aggregate with T row tiles form a chain of ~2.5 T tile-times
@@ -1121,6 +1265,17 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   const int occ = rep_occupancy(dim, pl->code);
   const int blocks_cu = std::min(4, occ);
   pl->rep_blocks = cus * blocks_cu;
+  if (pl->fast) {  // four waves per SIMD, the occupancy faml_fast_repulse is built for
+    int focc = 1;
+    dispatch_dim_narrow(dim, [&](auto Dc) {
+      constexpr int D = decltype(Dc)::value;
+      GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &focc, (const void*)faml_fast_repulse<D, kFastR>, kHT, 0));
+    });
+    pl->fast_blocks = cus * std::min(4, std::max(focc, 1));
+    pl->fitems.alloc(fitems.size());
+    pl->fitems.upload(fitems.data(), fitems.size(), st);
+  }
   std::vector<int> begs;
   begs.insert(begs.end(), beg_s.begin(), beg_s.end());
   pl->off_m = begs.size();
@@ -1192,6 +1347,65 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   GE_HIP(hipStreamSynchronize(st));
 }
 
+// One repulsion pass over the plan's streamed rows on stream ss: reads the
+// coordinates `cur` (P_T storage order) and DP, writes each row's sum to F at its
+// P_T position.  queue: a zeroed counter of its own for this launch.
+template <int D>
+static void faml_launch_repulse(ge_faml_plan* pl, hipStream_t ss, int* queue, const double* cur,
+                                double* F) {
+  const FaConst& c = pl->c;
+  if (pl->fast) {
+    if constexpr (D <= kNarrowMaxDim)  // fast is never set on the wide schedule
+      hipLaunchKernelGGL((faml_fast_repulse<D, kFastR>), dim3(pl->fast_blocks), dim3(kHT), 0, ss,
+                         pl->nfitems, pl->fitems.p, queue, pl->pt_ip, cur, pl->DP.p, c.repel, F);
+  } else if (pl->sym) {
+    if (pl->ntiles) GE_HIP(hipMemsetAsync(pl->prog.p, 0, sizeof(int) * pl->ntiles, ss));
+    double* H = pl->hand.p;  // hand-overs component-major (ge_sym.hpp sym_handover)
+    const size_t hs = (size_t)pl->n;
+    int* err = pl->sym_err.p;
+    const long long lim = pl->sym_limit;
+    if (!pl->stamp_path.empty()) {
+      if constexpr (D <= kNarrowMaxDim)  // sym is never set on the wide schedule
+        hipLaunchKernelGGL((faml_sym_repulse<D, false, true>), dim3(pl->sym_blocks), dim3(kSymT),
+                           0, ss, pl->nunits, pl->units.p, queue, pl->pt_ip, cur, pl->DP.p,
+                           c.repel, F, H, hs, pl->prog.p, err, lim, pl->stamps.p);
+    } else {
+      sym_repulse_launch(D, pl->sym_blocks, ss, pl->nunits, pl->units.p, queue, pl->pt_ip, cur,
+                         pl->DP.p, c.repel, F, H, hs, pl->prog.p, err, lim);
+    }
+  } else {
+    launch_big_repulse<D>(pl->code, pl->rep_blocks, ss, pl->nitems, pl->items.p, queue, pl->pt_ip,
+                          cur, pl->DP.p, c.repel, F, pl->wide);
+  }
+}
+
+// A hand-over wait of the symmetric sweeps that timed out fails the call.
+static void faml_check_sym(ge_faml_plan* pl, hipStream_t st) {
+  if (!pl->sym || pl->nunits <= 0) return;
+  int err = 0;
+  GE_HIP(hipMemcpyAsync(&err, pl->sym_err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  GE_HIP(hipStreamSynchronize(st));
+  if (err) {
+    GE_HIP(hipMemsetAsync(pl->sym_err.p, 0, sizeof(int), st));
+    throw Error(GE_ERR_STATE, "forceAtlasMultilevel: a symmetric sweep's hand-over wait timed out");
+  }
+}
+
+// ge_faml_plan_repulse: one pass on the caller's coordinates, on the context stream.
+// It uses the first queue counter, which every run zeroes again before its launches.
+static void faml_plan_repulse(ge_faml_plan* pl, const double* x, double* frep) {
+  hipStream_t st = pl->ctx->stream;
+  if (pl->nrows <= 0) return;
+  GE_HIP(hipMemsetAsync(pl->queue.p, 0, sizeof(int), st));
+  dispatch_dim(pl->dim, [&](auto Dc) {
+    constexpr int D = decltype(Dc)::value;
+    faml_launch_repulse<D>(pl, st, pl->queue.p, x, frep);
+  });
+  GE_HIP(hipGetLastError());
+  faml_check_sym(pl, st);
+  GE_HIP(hipStreamSynchronize(st));
+}
+
 static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, const double* init,
                           double* X) {
   hipStream_t st = pl->ctx->stream;
@@ -1255,28 +1469,7 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
         }
         const FamlRows<D> fr{pl->pt_ip, pl->pt_ix, pl->ecode.p, pl->ip, pl->vA, pl->dx,
                              cA, cur, pl->DP.p, pl->Fscr.p, nxt, pl->Fprev.p, c};
-        if (pl->sym) {
-          if (pl->ntiles) GE_HIP(hipMemsetAsync(pl->prog.p, 0, sizeof(int) * pl->ntiles, ss));
-          double* H = pl->hand.p;  // hand-overs component-major (ge_sym.hpp sym_handover)
-          const size_t hs = (size_t)pl->n;
-          int* err = pl->sym_err.p;
-          const long long lim = pl->sym_limit;
-          if (!pl->stamp_path.empty()) {
-            if constexpr (D <= kNarrowMaxDim)  // sym is never set on the wide schedule
-              hipLaunchKernelGGL((faml_sym_repulse<D, false, true>), dim3(pl->sym_blocks),
-                                 dim3(kSymT), 0, ss, pl->nunits, pl->units.p, pl->queue.p + it,
-                                 pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p, H, hs, pl->prog.p,
-                                 err, lim, pl->stamps.p);
-          } else {
-            sym_repulse_launch(D, pl->sym_blocks, ss, pl->nunits, pl->units.p, pl->queue.p + it,
-                               pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p, H, hs, pl->prog.p,
-                               err, lim);
-          }
-        } else {
-          launch_big_repulse<D>(pl->code, pl->rep_blocks, ss, pl->nitems, pl->items.p,
-                                pl->queue.p + it, pl->pt_ip, cur, pl->DP.p, c.repel, pl->Fscr.p,
-                                pl->wide);
-        }
+        faml_launch_repulse<D>(pl, ss, pl->queue.p + it, cur, pl->Fscr.p);
         if (re) GE_HIP(hipEventRecord(re[1], ss));
         hipEvent_t* ae = nullptr;
         if (pl->profiling) {
@@ -1311,16 +1504,7 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
     GE_HIP(hipStreamWaitEvent(st, pl->join[0], 0));
   });
   GE_HIP(hipGetLastError());
-  if (pl->sym && pl->nunits > 0) {  // a hand-over wait that timed out fails the call
-    int err = 0;
-    GE_HIP(hipMemcpyAsync(&err, pl->sym_err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    GE_HIP(hipStreamSynchronize(st));
-    if (err) {
-      GE_HIP(hipMemsetAsync(pl->sym_err.p, 0, sizeof(int), st));
-      throw Error(GE_ERR_STATE,
-                  "forceAtlasMultilevel: a symmetric sweep's hand-over wait timed out");
-    }
-  }
+  faml_check_sym(pl, st);
   if (!pl->stamp_path.empty() && pl->nunits > 0) {  // the last launch's timeline
     std::vector<long long> h((size_t)pl->nunits * kStampWords);
     GE_HIP(hipStreamSynchronize(st));
@@ -1401,6 +1585,7 @@ void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const
     pl->pt_ix = d_pt_ix;
     pl->vA = d_vA;
     pl->c = make_fa_const(p);
+    pl->mode = p.mode;
     std::vector<int> all(m);
     std::iota(all.begin(), all.end(), 0);
     faml_plan_build(pl, h_pt_ip, all);
@@ -1441,6 +1626,7 @@ static int faml_plan_create_impl(ge_ctx* ctx, int n, const int* d_ip, const int*
       pl->pt_ix = d_pt_ix;
       pl->vA = d_vA;
       pl->c = ge::make_fa_const(*p);
+      pl->mode = p->mode;
       ge::faml_plan_build(pl, h_pt_ip, aggs, split);
     } catch (...) {
       ge::faml_plan_free(pl);
@@ -1529,6 +1715,22 @@ int ge_faml_plan_run(ge_faml_plan* pl, const double* d_cA, const double* d_rA,
     GE_REQUIRE(pl && d_cA && d_rA && d_init && d_coords, "null argument");
     ge::DeviceGuard g(pl->ctx);
     ge::faml_plan_run(pl, d_cA, d_rA, d_init, d_coords);
+  });
+}
+
+int ge_faml_plan_repulse(ge_faml_plan* pl, const double* d_x, double* d_frep) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && d_x && d_frep, "null argument");
+    ge::DeviceGuard g(pl->ctx);
+    ge::faml_plan_repulse(pl, d_x, d_frep);
+  });
+}
+
+int ge_faml_plan_mode(ge_faml_plan* pl, int* mode, int* fast_items) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && mode && fast_items, "null argument");
+    *mode = pl->fast ? GE_MODE_FAST : GE_MODE_STRICT;
+    *fast_items = pl->nfitems;
   });
 }
 

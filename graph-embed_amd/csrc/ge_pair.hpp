@@ -215,6 +215,35 @@ __device__ __forceinline__ void rep_pair_fb(const double (&xi)[D], const double*
   if (!self) rep_pair<D, false, REPEL_ONE>(xi, xj, dip1, djp1, repel, acc);
 }
 
+// FAST mode's repulsion of j on i in closed form, added to row i's sum:
+// acc_k = fma(e_k, w, acc_k), e = x_i - x_j, w = dir * djp1 * y^3, with
+// y = 1 / max(|e|, eps) from v_rsq_f64 and two Newton steps; dir is the row's
+// (deg + 1) * repel.  s == 0 (the self pair, coincident members) gives rsq = inf,
+// NaN after the Newton steps, and fmin takes 1 / eps; e = 0 then makes the term 0.
+// Members closer than eps are clamped the same way (the reference's clamp_eps).
+// Every multiply-add is an explicit fma and nothing else can contract, so a row's
+// sum over partners j = 0, 1, ... has the same bits in every kernel that calls this
+// in that order (fa_repulse_fast, ge_fa.hip; faml_fast_repulse, ge_faml.hip).
+template <int D>
+__device__ __forceinline__ void fast_rep_pair(const double (&xi)[D], const double (&xj)[D],
+                                              double dir, double djp1, double (&acc)[D]) {
+  constexpr double inv_eps = 1.0 / kFaEps;
+  double e[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) e[k] = xi[k] - xj[k];
+  double s = e[0] * e[0];
+#pragma unroll
+  for (int k = 1; k < D; ++k) s = fma(e[k], e[k], s);
+  double y = __builtin_amdgcn_rsq(s);
+  const double hs = 0.5 * s;
+  y = y * fma(-hs * y, y, 1.5);
+  y = y * fma(-hs * y, y, 1.5);
+  y = fmin(y, inv_eps);
+  const double w = dir * djp1 * (y * y * y);
+#pragma unroll
+  for (int k = 0; k < D; ++k) acc[k] = fma(e[k], w, acc[k]);
+}
+
 // attraction_mag for linlog == 0 and delta == 1 (the defaults): no log / pow
 // code, which keeps register-tight kernels within their budget.
 __device__ __forceinline__ double attraction_mag_linear(double dis, double a, double dip1,

@@ -7,7 +7,8 @@
 // instead of std::random_device, and forceAtlasMultilevel draws in the
 // reference's single-thread order (the reference races on its generator across
 // OpenMP threads, :340-358).  The functions are inline (the reference defines
-// them non-inline in this header).
+// them non-inline in this header).  partition::setMode(GE_MODE_FAST) / $GE_MODE=fast
+// selects the tolerance mode of include/ge.h; the default is the reference's bits.
 #ifndef FORCEATLAS_HPP
 #define FORCEATLAS_HPP
 
@@ -59,6 +60,7 @@ inline void forceAtlas(const SparseMatrix& A, const int dim,
   p.tolerate = tolerate;
   p.normalize = normalize;
   p.seed = detail::seed_ref();
+  p.mode = detail::mode_ref();
   const int n = A.Rows();
   const bool init = coords.empty();
   std::vector<double> X = detail::flatten(coords, n, dim);
@@ -96,6 +98,7 @@ inline void forceAtlasMultilevel(const SparseMatrix& A, const SparseMatrix& P,
   p.delta = delta;
   p.tolerate = tolerate;
   p.seed = detail::seed_ref();
+  p.mode = detail::mode_ref();
   const int n = A.Rows();
   const int m = P.Rows();
   std::vector<double> cA = detail::flatten(coords_A, m, dim);

@@ -49,6 +49,19 @@ inline unsigned& seed_ref() {
   return s;
 }
 
+// The reference has one arithmetic; the drop-in runs GE_MODE_STRICT unless this
+// thread asks for GE_MODE_FAST ($GE_MODE = strict | fast, default strict;
+// partition::setMode).  Anything else in $GE_MODE is an error, not a silent default.
+inline int& mode_ref() {
+  thread_local int m = [] {
+    const char* e = std::getenv("GE_MODE");
+    if (!e || !*e || std::string(e) == "strict") return GE_MODE_STRICT;
+    if (std::string(e) == "fast") return GE_MODE_FAST;
+    throw std::runtime_error("graph-embed_amd: GE_MODE must be strict or fast");
+  }();
+  return m;
+}
+
 inline std::vector<double> flatten(const std::vector<std::vector<double>>& c, int n, int dim) {
   std::vector<double> out((size_t)n * dim, 0.0);
   for (int i = 0; i < n && i < (int)c.size(); ++i)
@@ -89,6 +102,15 @@ inline M from_ge_csr(ge_csr* c) {
 
 // Extension: fix the seed that replaces std::random_device in this thread.
 inline void setSeed(unsigned seed) { detail::seed_ref() = seed; }
+
+// Extension: GE_MODE_STRICT (the default, the reference's bits) or GE_MODE_FAST
+// (include/ge.h) for forceAtlas, forceAtlasMultilevel, embed and embedMultilevel
+// called from this thread.
+inline void setMode(int mode) {
+  if (mode != GE_MODE_STRICT && mode != GE_MODE_FAST)
+    throw std::invalid_argument("graph-embed_amd: setMode takes GE_MODE_STRICT or GE_MODE_FAST");
+  detail::mode_ref() = mode;
+}
 
 }  // namespace partition
 

@@ -118,6 +118,8 @@ _SIGS = {
                                                  ctypes.c_int, _i32p, ctypes.c_int,
                                                  ctypes.POINTER(_vp)]),
     "ge_faml_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ge_faml_plan_mode": (ctypes.c_int, [_vp, _ip, _ip]),
+    "ge_faml_plan_repulse": (ctypes.c_int, [_vp, _vp, _vp]),
     "ge_faml_plan_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ge_faml_plan_kernel_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double), _ip]),
@@ -602,6 +604,20 @@ class FamlPlan:
 
     def run(self, d_cA, d_rA, d_init, d_x):
         _check(lib().ge_faml_plan_run(self.h, _vp(d_cA), _vp(d_rA), _vp(d_init), _vp(d_x)))
+
+    def mode(self):
+        """(mode, fast_items): MODE_FAST only when the closed-form repulsion kernel is
+        scheduled for the streamed aggregates, with its row items per launch
+        (ge_faml_plan_mode); otherwise (MODE_STRICT, 0)."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        _check(lib().ge_faml_plan_mode(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def repulse(self, d_x, d_frep):
+        """One repulsion pass of the streamed aggregates on the coordinates d_x (n * dim,
+        P_T storage order) into d_frep, same layout; other members' positions are left
+        untouched (ge_faml_plan_repulse)."""
+        _check(lib().ge_faml_plan_repulse(self.h, _vp(d_x), _vp(d_frep)))
 
     def set_profiling(self, on):
         _check(lib().ge_faml_plan_set_profiling(self.h, int(on)))

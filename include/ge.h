@@ -30,7 +30,22 @@ extern "C" {
 #define GE_ERR_CAPACITY 1005 /* a device-side capacity limit (e.g. the partition's list pool) */
 
 #define GE_MODE_STRICT 0 /* bit-exact with the reference's serial op order */
-#define GE_MODE_FAST 1   /* re-associated / FMA / rsqrt; 1e-5 relative bar */
+/* GE_MODE_FAST: re-associated / FMA / rsqrt repulsion, everything else as STRICT.
+ * Single level (ge_force_atlas, ge_fa_plan_*): 1e-5 relative bar against STRICT.
+ * Multilevel level (ge_force_atlas_ml, ge_faml_plan_*, ge_embed and their *_dist
+ * forms), dim <= 4: the streamed aggregates' repulsion runs in closed form
+ * (faml_fast_repulse); resident aggregates, member rows, init, centring and radius
+ * steps are the STRICT kernels and stay bit-exact.  The bar there is PER ITERATION:
+ * each repulsion sum is within (s + 32) 2^-53 sum_j |t_ij| of the exact sum over the
+ * s members, and after 1 and 2 iterations the coordinates are within 1e-5 relative
+ * (max |dX| / max |X|) of STRICT on well-conditioned levels.  At the embed's horizon
+ * (100 iterations) no bar of that kind can hold for any re-association: the
+ * reference's own result moves by 1e-5 .. 0.3 (d = 2; 1e-5 .. 2e-2 at d = 3, ~1e-3 at
+ * d = 8) when its start is perturbed by 1e-15 .. 1e-12 relative (FAST
+ * mode), so FAST and STRICT are there two samples of the same chaotic dynamics.
+ * FAST results are deterministic and do not depend on how a plan is cut (whole,
+ * subset or shard plans give the same bits). */
+#define GE_MODE_FAST 1
 
 typedef struct ge_ctx ge_ctx;
 typedef struct ge_hier ge_hier;
@@ -68,7 +83,8 @@ int ge_ctx_sync(ge_ctx* ctx);
  * kernels, the fused per-iteration step (graph replay for long runs) and the
  * one-workgroup kernel in its general form (up to 256 rows): no persistent
  * coarsest-level kernel, no symmetric sweeps, and GE_MODE_FAST runs the STRICT
- * kernels (exact results satisfy its tolerance).
+ * kernels, single level and multilevel alike (exact results satisfy its tolerance;
+ * ge_faml_plan_mode then reports GE_MODE_STRICT).
  * GE_WIDE_MIN_DIM=<d> in the environment sends dim >= d (d <= 4) through that
  * schedule too: same results, for comparisons.  ge_embed_via_minimization_ml keeps
  * sending dim > 4 to its host path. */
@@ -158,12 +174,25 @@ int ge_faml_plan_create_shard(ge_ctx* ctx, ge_comm* comm, int n, const int* d_in
                               int n_aggs, const int* h_split, int n_split, ge_faml_plan** out);
 int ge_faml_plan_run(ge_faml_plan* plan, const double* d_coords_A, const double* d_r_A,
                      const double* d_init, double* d_coords);
+/* The mode the plan runs: GE_MODE_FAST only when faml_fast_repulse is scheduled (the
+ * caller asked for it, the plan has streamed rows and dim is not on the wide
+ * schedule), with the row items of one launch; otherwise GE_MODE_STRICT and 0.  Under
+ * FAST the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) are ignored and
+ * ge_faml_plan_schedule reports zeros. */
+int ge_faml_plan_mode(ge_faml_plan* plan, int* mode, int* fast_items);
+/* One repulsion pass of the plan's streamed aggregates alone (include/forceatlas.hpp:
+ * 394-410) on the caller's coordinates d_x (n*dim, P_T storage order): each streamed
+ * row's sum is written to d_frep in the same layout, positions of other members are
+ * left untouched.  Launches what ge_faml_plan_run launches per iteration, in either
+ * mode.  A measurement and test hook like ge_fa_plan_attract; it synchronises and
+ * does not disturb later runs. */
+int ge_faml_plan_repulse(ge_faml_plan* plan, const double* d_x, double* d_frep);
 int ge_faml_plan_set_profiling(ge_faml_plan* plan, int enable);
 /* Average device ms of the resident (LDS) kernels and of the streamed path per run. */
 int ge_faml_plan_kernel_ms(ge_faml_plan* plan, double* resident_ms, double* streamed_ms,
                            int* runs);
-/* Average device ms of one streamed-path repulsion launch (faml_big_repulse, one
- * per iteration) over the profiled runs, and the ordered pairs one launch
+/* Average device ms of one streamed-path repulsion launch (the sweeps, faml_big_repulse
+ * or, under GE_MODE_FAST, faml_fast_repulse; one per iteration) over the profiled runs, and the ordered pairs one launch
  * evaluates (sum of s(s-1) over the streamed aggregates); 0 launches if none. */
 int ge_faml_plan_repulse_ms(ge_faml_plan* plan, double* ms_per_launch, int* launches,
                             double* pairs_per_launch);
