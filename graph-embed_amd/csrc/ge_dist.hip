@@ -268,7 +268,8 @@ std::vector<char> split_aggregates(int m, const int* pip, const int* pix, const 
 }
 
 void fa_host_dist(ge_comm* c, int n, const int* ip, const int* ix, const double* dx, int dim,
-                  double* X, bool init_random, int iterations, const ge_fa_params& p) {
+                  double* X, bool init_random, int iterations, const ge_fa_params& p_in) {
+  const ge_fa_params p = far_as_fast(p_in);  // no far field on row shards (include/ge.h)
   if (init_random) uniform_stream(p.seed, (size_t)n * dim, X);  // :118-125
   if (c->nranks == 1 || n <= replica_max() || iterations <= 0) {
     fa_host(c->ctx, n, ip, ix, dx, dim, X, false, iterations, p);  // replicas

@@ -44,6 +44,7 @@
 #include <memory>
 #include <vector>
 
+#include "ge_far.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
 #include "ge_rows.hpp"
@@ -1470,6 +1471,11 @@ fa_grouped_stream(int n, int rb, int re, const int* __restrict__ ip, const int* 
 
 constexpr int kRowsPerThreadFast = 4;
 
+// GE_MODE_FARFIELD: the smallest level that runs the far field and the rows of a work
+// item (64 R), both from measurement (plan_init; DESIGN.md, FARFIELD mode).
+constexpr int kFarMinDefault = 131072;
+constexpr int kFarItemRows = 64;
+
 int device_cus() {
   int dev = 0, cus = 0;
   GE_HIP(hipGetDevice(&dev));
@@ -1707,7 +1713,11 @@ struct ge_fa_plan {
   ge::DevBuf<double> hand;
   int* sym_err_h = nullptr;  // pinned, device-mapped: a timed-out hand-over wait
   int* sym_err_d = nullptr;
+  // GE_MODE_FARFIELD (ge_far.hip): the engine when the far field runs, else why not
+  ge::FarEngine* far = nullptr;
+  int far_reason = GE_FAR_NOT_REQUESTED;
   ~ge_fa_plan() {
+    ge::far_destroy(far);
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     if (sym_err_h) (void)hipHostFree(sym_err_h);
   }
@@ -1719,13 +1729,13 @@ static void plan_init(ge_fa_plan* pl) {
   const int rows = pl->re - pl->rb;
   pl->cus = device_cus();
   pl->wide = wide_dim(pl->dim);
+  check_far_params(pl->p);
+  const bool far_req = pl->p.mode == GE_MODE_FARFIELD;
   // FAST is a tolerance-only mode and has no wide kernels: the exact ones satisfy it
   if (pl->wide) pl->p.mode = GE_MODE_STRICT;
   pl->dp1.alloc(pl->n);
   pl->frep.alloc((size_t)std::max(rows, 1) * pl->dim);
   pl->fprev.alloc((size_t)std::max(rows, 1) * pl->dim);
-  if (pl->p.mode == GE_MODE_FAST)
-    pl->fpart.alloc((size_t)std::max(rows, 1) * pl->dim * kFastJBlocks);
   hipStream_t s = pl->ctx->stream;
   if (rows > 0) {
     std::vector<int> h_ip(pl->re - pl->rb + 1), ids(rows), deg(rows), order;
@@ -1748,6 +1758,30 @@ static void plan_init(ge_fa_plan* pl) {
   hipLaunchKernelGGL(degp1_kernel, dim3((pl->n + 255) / 256), dim3(256), 0, s, pl->n, pl->ip,
                      pl->dx, pl->p.use_weights, pl->dp1.p);
   GE_HIP(hipGetLastError());
+  // The far field runs for a whole narrow level with positive masses from far_min
+  // vertices up; every other FARFIELD plan is a FAST plan (include/ge.h).  far_min: the
+  // smallest power of two from 2^13 at which FARFIELD beat FAST at d = 3, theta = 0.5 on
+  // an MI355X is 2^17 (ms per step, FAST / FARFIELD: 2^16 3.5 / 5.9, 2^17 13.9 / 12.0-12.5,
+  // 2^18 50 / 25-27, 2^20 780 / 112-116; profiles/r13/farfield_crossover.jsonl);
+  // GE_FAR_MIN overrides.  Items of 64 rows: 108-112 ms per C2 step against 231-268
+  // for 256 rows (same log; GE_FAR_R=1|4 overrides, tests and tuning).
+  if (far_req) {
+    int far_min = kFarMinDefault;
+    if (const char* e = std::getenv("GE_FAR_MIN")) far_min = std::atoi(e);
+    int item_rows = kFarItemRows;
+    if (const char* e = std::getenv("GE_FAR_R")) item_rows = std::atoi(e) == 1 ? 64 : std::atoi(e) == 4 ? 256 : item_rows;
+    pl->far_reason = pl->wide || pl->dim > kNarrowMaxDim ? GE_FAR_DIM
+                     : pl->rb != 0 || pl->re != pl->n    ? GE_FAR_ROW_SHARD
+                     : !far_masses_ok(s, pl->n, pl->dp1.p) ? GE_FAR_MASS
+                     : pl->n < far_min                    ? GE_FAR_SMALL
+                                                          : GE_FAR_ACTIVE;
+    if (pl->far_reason == GE_FAR_ACTIVE)
+      pl->far = far_create(s, pl->n, pl->dim, pl->p.theta, item_rows, pl->cus);
+    else if (pl->p.mode == GE_MODE_FARFIELD)
+      pl->p.mode = GE_MODE_FAST;
+  }
+  if (pl->p.mode == GE_MODE_FAST || pl->far)  // the far field's non-finite iterations run FAST
+    pl->fpart.alloc((size_t)std::max(rows, 1) * pl->dim * kFastJBlocks);
   GE_HIP(hipMemsetAsync(pl->fprev.p, 0, sizeof(double) * pl->fprev.n, s));
   // Symmetric repulsion: STRICT, every row on this plan (a row shard keeps the
   // ordered-pair kernel), and a level past the grouped / streamed kernels.
@@ -1804,6 +1838,25 @@ static void sym_check(ge_fa_plan* pl) {
   }
 }
 
+// The repulsion launch of one iteration into frep (rows [rb, re)): the symmetric
+// sweeps, the far field (FAST's kernels in an iteration whose box is not finite) or
+// the mode's ordered-pair kernels.
+template <int D>
+static void plan_repulse_into(ge_fa_plan* pl, hipStream_t s, const double* xc, double* frep) {
+  if (pl->sym) {  // never on the wide schedule (plan_init)
+    sym_prepare(pl);
+    sym_check(pl);
+    GE_HIP(hipMemsetAsync(pl->ctl.p, 0, sizeof(int) * pl->ctl.n, s));
+    sym_repulse_launch(D, pl->sym_blocks, s, pl->sym_units, pl->units.p, pl->ctl.p, pl->seg.p, xc,
+                       pl->dp1.p, pl->p.repel, frep, pl->hand.p, (size_t)pl->n, pl->ctl.p + 1,
+                       pl->sym_err_d, pl->sym_limit);
+  } else if (pl->far && far_repulse(pl->far, s, xc, pl->dp1.p, pl->p.repel, frep)) {
+  } else {
+    launch_repulsion<D>(s, pl->far ? GE_MODE_FAST : pl->p.mode, pl->n, pl->rb, pl->re, xc,
+                        pl->dp1.p, pl->p.repel, frep, pl->fpart.p, pl->cus, pl->wide);
+  }
+}
+
 static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
   hipStream_t s = pl->ctx->stream;
   hipEvent_t* ev = nullptr;
@@ -1827,17 +1880,7 @@ static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
       if (ev) GE_HIP(hipEventRecord(ev[1], s));
       return;
     }
-    if (pl->sym) {  // never on the wide schedule (plan_init)
-      sym_prepare(pl);
-      sym_check(pl);
-      GE_HIP(hipMemsetAsync(pl->ctl.p, 0, sizeof(int) * pl->ctl.n, s));
-      sym_repulse_launch(D, pl->sym_blocks, s, pl->sym_units, pl->units.p, pl->ctl.p,
-                         pl->seg.p, xc, pl->dp1.p, pl->p.repel, pl->frep.p, pl->hand.p,
-                         (size_t)pl->n, pl->ctl.p + 1, pl->sym_err_d, pl->sym_limit);
-    } else {
-      launch_repulsion<D>(s, pl->p.mode, pl->n, pl->rb, pl->re, xc, pl->dp1.p, pl->p.repel,
-                          pl->frep.p, pl->fpart.p, pl->cus, pl->wide);
-    }
+    plan_repulse_into<D>(pl, s, xc, pl->frep.p);
     if (ev) GE_HIP(hipEventRecord(ev[1], s));
     launch_attract<D>(s, pl->rc, pl->rstreams, pl->rb, pl->ip, pl->ix, pl->dx, xc, pl->dp1.p, pl->frep.p,
                       pl->fprev.p, xn, pl->c);
@@ -2091,7 +2134,8 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
   // kGraphSteps iterations: host launch overhead would otherwise dominate the
   // microsecond-scale kernels of a small level.
   constexpr int kGraphSteps = 32;  // even: the buffers are back in place after a replay
-  if (iterations >= 4 * kGraphSteps && !std::getenv("GE_NO_GRAPH")) {
+  // (not with the far field: its pass synchronises once, include/ge.h)
+  if (iterations >= 4 * kGraphSteps && !pl.far && !std::getenv("GE_NO_GRAPH")) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     GE_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -2172,6 +2216,60 @@ int ge_fa_plan_attract(ge_fa_plan* pl, const double* xc, const double* frep, dou
     GE_REQUIRE(pl && xc && xn && frep && xc != xn, "bad plan attract arguments");
     ge::DeviceGuard g(pl->ctx);
     ge::plan_attract(pl, xc, frep, xn);
+  });
+}
+
+int ge_fa_plan_repulse(ge_fa_plan* pl, const double* x, double* frep) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && x && frep, "bad plan repulse arguments");
+    ge::DeviceGuard g(pl->ctx);
+    hipStream_t s = pl->ctx->stream;
+    ge::dispatch_dim(pl->dim, [&](auto Dc) {
+      ge::plan_repulse_into<decltype(Dc)::value>(pl, s, x, frep);
+    });
+    GE_HIP(hipGetLastError());
+    GE_HIP(hipStreamSynchronize(s));
+    ge::sym_check(pl);
+  });
+}
+
+int ge_fa_plan_far_info(ge_fa_plan* pl, int* active, int* reason, double* theta, int* item_rows,
+                        int* levels, int* level_cells, long long* level_points, int* fallback,
+                        long long* accepted, long long* exact_leaves, long long* pair_terms,
+                        double* prep_ms, double* item_ms) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl, "null plan");
+    ge::DeviceGuard g(pl->ctx);
+    if (active) *active = pl->far ? 1 : 0;
+    if (reason) *reason = pl->far_reason;
+    if (pl->far) {
+      ge::far_info(pl->far, pl->ctx->stream, theta, item_rows, levels, level_cells, level_points,
+                   fallback, accepted, exact_leaves, pair_terms, prep_ms, item_ms);
+      return;
+    }
+    if (theta) *theta = pl->p.theta;
+    if (item_rows) *item_rows = 0;
+    if (levels) *levels = 0;
+    for (int l = 0; l < GE_FAR_MAX_LEVELS; ++l) {
+      if (level_cells) level_cells[l] = 0;
+      if (level_points) level_points[l] = 0;
+      if (accepted) accepted[l] = 0;
+    }
+    if (fallback) *fallback = 0;
+    if (exact_leaves) *exact_leaves = 0;
+    if (pair_terms) *pair_terms = 0;
+    if (prep_ms) *prep_ms = 0.0;
+    if (item_ms) *item_ms = 0.0;
+  });
+}
+
+int ge_fa_plan_far_layout(ge_fa_plan* pl, int* perm, unsigned long long* keys, double* box,
+                          double* cells, double* items) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl, "null plan");
+    ge::DeviceGuard g(pl->ctx);
+    if (!pl->far) throw ge::Error(GE_ERR_STATE, "the far field does not run on this plan");
+    ge::far_layout(pl->far, pl->ctx->stream, perm, keys, box, cells, items);
   });
 }
 

@@ -1585,7 +1585,7 @@ void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const
     pl->pt_ix = d_pt_ix;
     pl->vA = d_vA;
     pl->c = make_fa_const(p);
-    pl->mode = p.mode;
+    pl->mode = far_as_fast(p).mode;
     std::vector<int> all(m);
     std::iota(all.begin(), all.end(), 0);
     faml_plan_build(pl, h_pt_ip, all);
@@ -1626,7 +1626,7 @@ static int faml_plan_create_impl(ge_ctx* ctx, int n, const int* d_ip, const int*
       pl->pt_ix = d_pt_ix;
       pl->vA = d_vA;
       pl->c = ge::make_fa_const(*p);
-      pl->mode = p->mode;
+      pl->mode = ge::far_as_fast(*p).mode;
       ge::faml_plan_build(pl, h_pt_ip, aggs, split);
     } catch (...) {
       ge::faml_plan_free(pl);

@@ -270,7 +270,7 @@ void embed_impl(ge_ctx* ctx, ge_comm* comm, int levels, const int* a_n, const in
   auto fa_level = [&](int n, const int* ip, const int* ix, const double* dx, int d, double* X,
                       bool init, int it, const ge_fa_params& pr) {
     if (dist) fa_host_dist(comm, n, ip, ix, dx, d, X, init, it, pr);
-    else fa_host(ctx, n, ip, ix, dx, d, X, init, it, pr);
+    else fa_host(ctx, n, ip, ix, dx, d, X, init, it, far_as_fast(pr));
   };
   auto faml_level = [&](int n, const int* ip, const int* ix, const double* dx, int m,
                         const int* pip, const int* pix, const int* vA, const double* cA,
@@ -405,6 +405,7 @@ void ge_fa_params_default(ge_fa_params* p) {
   p->normalize = 0;
   p->seed = 12345u;
   p->mode = GE_MODE_STRICT;
+  p->theta = 0.5;
 }
 
 int ge_device_count(int* count) {

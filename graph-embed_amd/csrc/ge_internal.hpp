@@ -35,6 +35,20 @@ void set_last_error(const std::string& msg);
     if (!(cond)) throw ::ge::Error(GE_ERR_ARG, (msg));        \
   } while (0)
 
+// GE_MODE_FARFIELD's parameter (include/ge.h); read in no other mode.
+inline void check_far_params(const ge_fa_params& p) {
+  if (p.mode != GE_MODE_FARFIELD) return;
+  GE_REQUIRE(p.theta >= 0.0 && p.theta < 1.0,  // false for NaN
+             "GE_MODE_FARFIELD: theta must be finite and in 0 <= theta < 1");
+}
+// The entry points without a far field (the multilevel level, embed, the sharded
+// forms) run GE_MODE_FARFIELD as GE_MODE_FAST.
+inline ge_fa_params far_as_fast(ge_fa_params p) {
+  check_far_params(p);
+  if (p.mode == GE_MODE_FARFIELD) p.mode = GE_MODE_FAST;
+  return p;
+}
+
 template <class F>
 int guarded(F&& f) {
   try {

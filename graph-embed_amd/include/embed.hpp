@@ -57,6 +57,7 @@ inline std::vector<std::vector<double>> embed(const std::vector<SparseMatrix>& A
   ge_fa_params_default(&p);
   p.seed = detail::seed_ref();
   p.mode = detail::mode_ref();  // embedMultilevel takes it through forceAtlas[Multilevel]
+  p.theta = detail::theta_ref();
   std::vector<double> X((size_t)As[0].Rows() * d);
   detail::check(ge_embed(detail::context(), levels, a_n.data(), a_off.data(), a_nz.data(),
                          a_ip.data(), a_ix.data(), a_dx.data(), p_rows.data(), p_off.data(),

@@ -7,8 +7,9 @@
 // instead of std::random_device, and forceAtlasMultilevel draws in the
 // reference's single-thread order (the reference races on its generator across
 // OpenMP threads, :340-358).  The functions are inline (the reference defines
-// them non-inline in this header).  partition::setMode(GE_MODE_FAST) / $GE_MODE=fast
-// selects the tolerance mode of include/ge.h; the default is the reference's bits.
+// them non-inline in this header).  partition::setMode(GE_MODE_FAST | GE_MODE_FARFIELD)
+// / $GE_MODE=fast | farfield (the latter with partition::setTheta / $GE_THETA) selects
+// a tolerance mode of include/ge.h; the default is the reference's bits.
 #ifndef FORCEATLAS_HPP
 #define FORCEATLAS_HPP
 
@@ -61,6 +62,7 @@ inline void forceAtlas(const SparseMatrix& A, const int dim,
   p.normalize = normalize;
   p.seed = detail::seed_ref();
   p.mode = detail::mode_ref();
+  p.theta = detail::theta_ref();
   const int n = A.Rows();
   const bool init = coords.empty();
   std::vector<double> X = detail::flatten(coords, n, dim);
@@ -99,6 +101,7 @@ inline void forceAtlasMultilevel(const SparseMatrix& A, const SparseMatrix& P,
   p.tolerate = tolerate;
   p.seed = detail::seed_ref();
   p.mode = detail::mode_ref();
+  p.theta = detail::theta_ref();
   const int n = A.Rows();
   const int m = P.Rows();
   std::vector<double> cA = detail::flatten(coords_A, m, dim);

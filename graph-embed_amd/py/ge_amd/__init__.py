@@ -30,6 +30,10 @@ HEADER = os.path.join(REPO_ROOT, "include", "ge.h")
 
 MODE_STRICT = 0
 MODE_FAST = 1
+MODE_FARFIELD = 2
+FAR_MAX_LEVELS = 8  # GE_FAR_MAX_LEVELS
+# ge_fa_plan_far_info reason codes (GE_FAR_*)
+FAR_REASONS = ("active", "not_requested", "dim", "row_shard", "mass", "small")
 MATH_OPS = {"sqrt": 0, "div": 1, "pair": 2, "rep": 3}  # GE_MATH_*
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -46,7 +50,7 @@ class FaParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_double) for k in
                 ("ks", "ksmax", "repel", "attract", "gravity", "delta", "tolerate")] + \
                [(k, ctypes.c_int) for k in ("use_weights", "linlog", "nohubs", "normalize")] + \
-               [("seed", ctypes.c_uint), ("mode", ctypes.c_int)]
+               [("seed", ctypes.c_uint), ("mode", ctypes.c_int), ("theta", ctypes.c_double)]
 
 
 _SIGS = {
@@ -66,6 +70,15 @@ _SIGS = {
                                          ctypes.c_int, ctypes.POINTER(_vp)]),
     "ge_fa_plan_step": (ctypes.c_int, [_vp, _vp, _vp]),
     "ge_fa_plan_attract": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "ge_fa_plan_repulse": (ctypes.c_int, [_vp, _vp, _vp]),
+    "ge_fa_plan_far_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_double), _ip, _ip,
+                                           _ip, ctypes.POINTER(ctypes.c_longlong), _ip,
+                                           ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]),
+    "ge_fa_plan_far_layout": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "ge_fa_plan_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ge_fa_plan_kernel_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), _ip]),
@@ -687,6 +700,7 @@ class FaPlan:
 
     def __init__(self, ctx, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw):
         self.ctx = ctx
+        self.n, self.dim = n, dim
         p = params(**kw)
         h = _vp()
         _check(lib().ge_fa_plan_create(ctx.h, n, nnz, _vp(d_ip), _vp(d_ix), _vp(d_dx), dim,
@@ -700,6 +714,53 @@ class FaPlan:
         """Attraction + gravity + update alone on supplied repulsion sums
         (ge_fa_plan_attract)."""
         _check(lib().ge_fa_plan_attract(self.h, _vp(d_x_cur), _vp(d_frep), _vp(d_x_next)))
+
+    def repulse(self, d_x, d_frep):
+        """One repulsion pass alone on the coordinates d_x (n * dim) into d_frep (the
+        plan's rows * dim), in the plan's mode (ge_fa_plan_repulse)."""
+        _check(lib().ge_fa_plan_repulse(self.h, _vp(d_x), _vp(d_frep)))
+
+    def far_info(self):
+        """ge_fa_plan_far_info: active, reason (FAR_REASONS), theta, item_rows, levels,
+        level_cells / level_points per level (leaves first) and, of the last pass,
+        fallback, accepted (cells per level), exact_leaves, pair_terms, prep_ms, item_ms."""
+        act, why, rows, lv, fb = (ctypes.c_int() for _ in range(5))
+        th, prep, item = (ctypes.c_double() for _ in range(3))
+        cells = (ctypes.c_int * FAR_MAX_LEVELS)()
+        pts, acc = (ctypes.c_longlong * FAR_MAX_LEVELS)(), (ctypes.c_longlong * FAR_MAX_LEVELS)()
+        leaves, terms = ctypes.c_longlong(), ctypes.c_longlong()
+        _check(lib().ge_fa_plan_far_info(
+            self.h, ctypes.byref(act), ctypes.byref(why), ctypes.byref(th), ctypes.byref(rows),
+            ctypes.byref(lv), cells, pts, ctypes.byref(fb), acc, ctypes.byref(leaves),
+            ctypes.byref(terms), ctypes.byref(prep), ctypes.byref(item)))
+        L = lv.value
+        return {"active": bool(act.value), "reason": FAR_REASONS[why.value], "theta": th.value,
+                "item_rows": rows.value, "levels": L, "level_cells": list(cells)[:L],
+                "level_points": list(pts)[:L], "fallback": bool(fb.value),
+                "accepted": list(acc)[:L], "exact_leaves": leaves.value,
+                "pair_terms": terms.value, "prep_ms": prep.value, "item_ms": item.value}
+
+    def far_layout(self):
+        """ge_fa_plan_far_layout: what the last far-field pass used.  perm (the vertex at
+        each sorted position), keys (sorted Morton keys), box (lower corner, key scale),
+        cells (one array per level, leaves first, rows {c_0 .. c_{d-1}, M, a}) and items
+        (same rows; item q holds sorted rows [q item_rows, (q + 1) item_rows))."""
+        info = self.far_info()
+        if not info["active"]:
+            raise GeError("the far field does not run on this plan: " + info["reason"])
+        n, d = self.n, self.dim
+        nitems = -(-n // info["item_rows"])
+        perm = np.empty(n, dtype=np.int32)
+        keys = np.empty(n, dtype=np.uint64)
+        box = np.empty(d + 1)
+        cells = np.empty((sum(info["level_cells"]), d + 2))
+        items = np.empty((nitems, d + 2))
+        _check(lib().ge_fa_plan_far_layout(self.h, *(a.ctypes.data_as(_vp)
+                                                     for a in (perm, keys, box, cells, items))))
+        offs = np.cumsum([0] + info["level_cells"])
+        return {"perm": perm, "keys": keys, "box": box, "items": items,
+                "item_rows": info["item_rows"], "theta": info["theta"],
+                "cells": [cells[offs[l]:offs[l + 1]] for l in range(info["levels"])]}
 
     def set_profiling(self, on):
         _check(lib().ge_fa_plan_set_profiling(self.h, int(on)))

@@ -46,6 +46,37 @@ extern "C" {
  * FAST results are deterministic and do not depend on how a plan is cut (whole,
  * subset or shard plans give the same bits). */
 #define GE_MODE_FAST 1
+/* GE_MODE_FARFIELD: GE_MODE_FAST with a Barnes-Hut style far field for the single
+ * level's repulsion (ge_force_atlas, ge_fa_plan_*; graph-embed_amd/csrc/ge_far.hip).
+ * What is approximated: every iteration the vertices are sorted along a Morton curve
+ * and summarised in a flat hierarchy (leaves of 64 sorted vertices, 16 cells per
+ * parent; a cell C has mass M_C = sum (deg_j + 1), centre c_C = sum (deg_j + 1) x_j /
+ * M_C and a radius a_C >= max_j |x_j - c_C|).  A work item I (64 or 256 consecutive
+ * sorted rows with centre c_I and radius a_I) replaces the members of a cell by one
+ * term of mass M_C at c_C when, with Dist = |c_I - c_C|,
+ *     a_C <= theta (Dist - a_I)   and   Dist - a_I - a_C >= 1e-5
+ * (the second condition: no pair the reference would clamp is ever approximated);
+ * otherwise it descends, and a leaf that is not accepted is evaluated pair by pair
+ * with FAST's closed-form term.  The decision is made once per item, never per row.
+ * The bound, per row i with d_i = (deg_i + 1) repel, A_i the cells accepted for its
+ * item, rho = |x_i - c_C|, mu_C = |sum_j m_j (x_j - c_C)|, S_C = sum_j m_j |x_j - c_C|^2
+ * and a*_C = max_j |x_j - c_C|:
+ *     |F~_i - F_i|_2 <= d_i sum_{C in A_i} [ 2 mu_C / rho^3 + 3 S_C / (rho - a*_C)^4 ]
+ *                       + (terms_i + 24) 2^-53 sum |t~|
+ * against the exact clamped sum of include/forceatlas.hpp:148-167 (first-order Taylor
+ * expansion of x / |x|^3 about x_i - c_C; derivation in tests/test_far_cases.py).
+ * Results are deterministic: a row's sum is one lane's chain over cells ascending,
+ * children ascending, members ascending.
+ * The far field runs when dim <= 4 (not the wide schedule), the plan holds every row
+ * (row_begin = 0, row_end = n), every deg_j + 1 is > 0 and n >= far_min (131 072, the
+ * measured crossover against FAST at dim 3; GE_FAR_MIN overrides).  In every other case -- row shards and ge_force_atlas_dist,
+ * dim >= 5, a non-positive mass, a small level -- and in an iteration whose bounding
+ * box is not finite, the plan runs exactly what GE_MODE_FAST runs, with the same bits.
+ * ge_faml_plan_*, ge_force_atlas_ml, ge_embed and their *_dist forms treat it as
+ * GE_MODE_FAST.  theta is ge_fa_params.theta, 0 <= theta < 1.  An iteration of this
+ * mode synchronises the stream once (the box check), so its steps cannot be captured
+ * into a graph; ge_force_atlas does not capture them. */
+#define GE_MODE_FARFIELD 2
 
 typedef struct ge_ctx ge_ctx;
 typedef struct ge_hier ge_hier;
@@ -58,7 +89,9 @@ typedef struct ge_fa_params {
   double ks, ksmax, repel, attract, gravity, delta, tolerate;
   int use_weights, linlog, nohubs, normalize;
   unsigned seed; /* mt19937 seed replacing std::random_device (:104-105, :332-333) */
-  int mode;      /* GE_MODE_STRICT (default) or GE_MODE_FAST */
+  int mode;      /* GE_MODE_STRICT (default), GE_MODE_FAST or GE_MODE_FARFIELD */
+  double theta;  /* GE_MODE_FARFIELD's opening parameter, 0 <= theta < 1 (default 0.5, the
+                    conventional Barnes-Hut value); not read in any other mode */
 } ge_fa_params;
 
 void ge_fa_params_default(ge_fa_params* p);
@@ -125,6 +158,42 @@ int ge_fa_plan_set_profiling(ge_fa_plan* plan, int enable);
  * since profiling was enabled; *launches = steps timed. Synchronises. */
 int ge_fa_plan_kernel_ms(ge_fa_plan* plan, double* repulsion_ms, double* attraction_ms,
                          int* launches);
+/* One repulsion pass alone (include/forceatlas.hpp:151-167) on the caller's
+ * coordinates d_x (n*dim): rows [row_begin, row_end) of the sums go to d_frep
+ * ((row_end - row_begin)*dim), what ge_fa_plan_attract takes.  Launches what
+ * ge_fa_plan_step launches for the repulsion, in any mode (the fused small-level
+ * STRICT step has no separate repulsion: there the ordered-pair kernels run, with the
+ * same bits).  The single-level twin of ge_faml_plan_repulse; it synchronises. */
+int ge_fa_plan_repulse(ge_fa_plan* plan, const double* d_x, double* d_frep);
+/* GE_MODE_FARFIELD diagnostics.  active: the far field runs; reason: why not
+ * (GE_FAR_*).  theta, rows per work item, the levels of the hierarchy (0 = leaves)
+ * with each level's cell count and cell size in points (arrays of GE_FAR_MAX_LEVELS).
+ * Of the last pass: fallback (1: the bounding box was not finite and the FAST kernels
+ * ran; the counters are then zero), cells accepted per level, leaves evaluated pair by
+ * pair and pair terms evaluated, each summed over the work items (a few atomics per
+ * item), and the device ms of the pass before the item kernel (box, keys, sort,
+ * records, summaries) and of the item kernel.  Any output pointer may be NULL.
+ * Synchronises. */
+#define GE_FAR_MAX_LEVELS 8
+#define GE_FAR_ACTIVE 0
+#define GE_FAR_NOT_REQUESTED 1 /* mode is not GE_MODE_FARFIELD */
+#define GE_FAR_DIM 2           /* dim >= 5 or the wide schedule */
+#define GE_FAR_ROW_SHARD 3     /* the plan does not hold every row */
+#define GE_FAR_MASS 4          /* some deg + 1 is not > 0 */
+#define GE_FAR_SMALL 5         /* n < far_min */
+int ge_fa_plan_far_info(ge_fa_plan* plan, int* active, int* reason, double* theta,
+                        int* item_rows, int* levels, int* level_cells, long long* level_points,
+                        int* fallback, long long* accepted, long long* exact_leaves,
+                        long long* pair_terms, double* prep_ms, double* item_ms);
+/* What the last far-field pass used, copied to the host: perm (n: the vertex at each
+ * sorted position), keys (n, sorted Morton keys), box (dim + 1: the lower corner and
+ * the key scale), cells (per level from the leaves up, level_cells[l] records of
+ * dim + 2 doubles {c_0 .. c_{dim-1}, M, a}) and items (ceil(n / item_rows) records of
+ * the same form; item q holds the sorted rows [q item_rows, min(n, (q + 1) item_rows))).
+ * Any pointer may be NULL.  GE_ERR_STATE unless the far field is active and a pass has
+ * run without falling back.  Synchronises. */
+int ge_fa_plan_far_layout(ge_fa_plan* plan, int* perm, unsigned long long* keys, double* box,
+                          double* cells, double* items);
 int ge_fa_plan_destroy(ge_fa_plan* plan);
 
 /* ---- multilevel ForceAtlas ----
