@@ -102,18 +102,29 @@ struct PairDen {
   double dis;
   Recip rdis, rdd;  // {dis, ~1/dis}, {dis * dis, ~1/dis^2}
 };
-__device__ __forceinline__ PairDen pair_den(double s) {
+// sqrt_normal(s) (ge_math.hpp: the same sequence) that also hands out its Goldschmidt
+// half-reciprocal h1 ~ 1 / (2 sqrt(s)).  NaN for s == 0.  NEG: -sqrt_normal(s) from the
+// last fma with both addends negated -- the same rounding of the negated sum, so the
+// negated bits for every s > 0 -- for callers that only ever use the root negated.
+template <bool NEG = false>
+__device__ __forceinline__ double sqrt_half_recip(double s, double& h1) {
   const double y = __builtin_amdgcn_rsq(s);
   const double g0 = s * y;
   const double h0 = y * 0.5;
   const double r0 = __builtin_fma(-h0, g0, 0.5);
-  const double h1 = __builtin_fma(h0, r0, h0);
+  h1 = __builtin_fma(h0, r0, h0);
   const double g1 = __builtin_fma(g0, r0, g0);
   const double d0 = __builtin_fma(-g1, g1, s);
   const double g2 = __builtin_fma(d0, h1, g1);
   const double d1 = __builtin_fma(-g2, g2, s);
+  return NEG ? __builtin_fma(-d1, h1, -g2) : __builtin_fma(d1, h1, g2);
+}
+
+// pair_den from the unclamped root g3 and h1: the clamps, the Newton steps and the
+// all-ones correction.
+__device__ __forceinline__ PairDen pair_den_from(double g3, double h1) {
   // sqrt_normal(s), clamped (s == 0: NaN, and fmax takes eps)
-  const double dis = fmax(__builtin_fma(d1, h1, g2), kFaEps);
+  const double dis = fmax(g3, kFaEps);
   const double y0 = fmin(h1 + h1, 1e5);
   const double yd = __builtin_fma(y0, __builtin_fma(-dis, y0, 1.0), y0);
   const double dd = dis * dis;
@@ -127,15 +138,92 @@ __device__ __forceinline__ PairDen pair_den(double s) {
   const double yr = __hiloint2double(__double2hiint(yd), ones ? 1 : __double2loint(yd));
   return PairDen{dis, Recip{dis, yr}, Recip{dd, ydd}};
 }
+__device__ __forceinline__ PairDen pair_den(double s) {
+  double h1;
+  const double g3 = sqrt_half_recip(s, h1);
+  return pair_den_from(g3, h1);
+}
+
+// pair_den in detect-then-fix form (round 14): the same bits, five instructions fewer
+// per pair where no lane of the wave needs them.  Of pair_den's instructions the two
+// clamps (fmax, fmin) and the all-ones correction (frexp_mant, compare, select) change
+// a bit only for a pair closer than eps (or coincident: g3 NaN) and for a distance
+// whose significand is all ones.  Here each lane computes the unclamped, uncorrected
+// values and two flags,
+//   low    !(g3 >= kFaDetect), kFaDetect = eps (1 + 2^-20): true for NaN too;
+//   ones   the low word of g3 is 0xFFFFFFFF: necessary for an all-ones significand
+//          (true by chance for one distance in 2^32),
+// and when any lane of the wave has one set (a wave-uniform branch on the two compare
+// masks: no exec-mask divergence, `fixed` reports it), every lane takes
+// pair_den_from(g3, h1) instead -- pair_den's own code on pair_den's own g3 and h1,
+// hence its bits.  A lane with neither flag set gets pair_den's bits without it,
+// because every instruction left out was an identity for it:
+//   fmax   g3 >= kFaDetect > eps and g3 is not NaN, so fmax(g3, eps) = g3;
+//   fmin   h1 is one Newton step of v_rsq_f64, 2 h1 = (1 + d) / sqrt(s) with |d| far
+//          below 2^-21 (the step squares the estimate's error: the bound holds for
+//          any estimate good to 2^-11, and v_rsq_f64's is ~2^-26), and g3 =
+//          RN(sqrt(s)) >= eps (1 + 2^-20) gives sqrt(s) >= eps (1 + 2^-20)(1 - 2^-53),
+//          so 2 h1 <= (1 / eps)(1 + 2^-21)(1 + 2^-52) / (1 + 2^-20) < 1e5 (1 - 2^-22)
+//          with eps = RN(1e-5) within 2^-53 of 1e-5: fmin(2 h1, 1e5) = 2 h1.  (At
+//          g3 == eps itself the margin is not clean -- 2 h1 may exceed 1e5 by an ulp
+//          -- which is why the flag is wider than the clamp);
+//   select the low word is not all ones, so the significand is not: yr = yd.
+// The rare block rewrites the four results in place and nothing else stays live for
+// it but g3 and h1.  (Measured and not kept, DESIGN.md 5i: the compares issued with the
+// reciprocals, the masks held in scalar registers through the quotients and the branch
+// after the term's last multiply, the rare block redoing the whole term -- the wave
+// then never waits for its flags, and it ran 0.3-0.7 ms slower than the branch right
+// after the root.)  Callers: the sweeps' tile_steps (ge_sym.hpp), whose rows never meet
+// themselves.  A kernel in which every row meets its own column in each block (the
+// diagonal tiles, the resident, packed and one-workgroup kernels) would take the
+// branch every time and keeps pair_den.
+constexpr double kFaDetect = kFaEps * (1.0 + 0x1p-20);
+// Every use of the two denominators is a negated one (the Newton steps, div_by_nz's
+// remainders fma(-d, q, n)), so this form keeps them negated: ndis = -dis from the
+// root's last fma with both addends negated, ndd = ndis * -ndis.  (With dis itself
+// joined across a branch the compiler copied -dis into a second register pair on the
+// common path, two moves per pair.)
+struct PairDenNeg {
+  double ndis, yd, ndd, ydd;  // -dis, ~1/dis, -(dis * dis), ~1/dis^2
+};
+// div_by_nz(num, Recip{-nd, y}): the same instructions.
+__device__ __forceinline__ double div_by_nz_neg(double num, double nd, double y) {
+  const double q = num * y;
+  const double rem = __builtin_fma(nd, q, num);
+  return __builtin_fma(rem, y, q);
+}
+__device__ __forceinline__ PairDenNeg pair_den_detect(double s, bool& fixed) {
+  double h1;
+  const double ng3 = sqrt_half_recip<true>(s, h1);
+  const double y0 = h1 + h1;
+  const double yd = __builtin_fma(y0, __builtin_fma(ng3, y0, 1.0), y0);
+  const double ndd = ng3 * -ng3;
+  const double z0 = yd * yd;
+  const double ydd = __builtin_fma(z0, __builtin_fma(ndd, z0, 1.0), z0);
+  PairDenNeg pn{ng3, yd, ndd, ydd};
+  const bool low = !(ng3 <= -kFaDetect);
+  const bool ones = __double2loint(ng3) == -1;
+  fixed = __builtin_amdgcn_ballot_w64(low || ones) != 0;
+  if (__builtin_expect(fixed, 0)) {
+    const PairDen pd = pair_den_from(-ng3, h1);
+    pn = PairDenNeg{-pd.dis, pd.rdis.y, -pd.rdd.ds, pd.rdd.y};
+    // opaque: keeps this block a plain out-of-line detour that rewrites the four
+    // values in place (without it the join came out with two register copies)
+    asm volatile("" : "+v"(pn.ndis), "+v"(pn.ndd));
+  }
+  return pn;
+}
 
 // Repulsion of j on i (:152-166): the term added to row i's sum, out[k] =
 // (e_k / dis) * val.  e = x_i - x_j equals -(x_j - x_i) up to the sign of zero,
 // and a zero term never changes the sum (see ge_fa.hip); the j == i term is
-// +-0 for the same reason.
-template <int D, bool SHARED, bool REPEL_ONE>
+// +-0 for the same reason.  DETECT (with SHARED): the detect-then-fix form of the
+// denominators (pair_den_detect), and *fixed says whether the wave took its fix-up.
+template <int D, bool SHARED, bool REPEL_ONE, bool DETECT = false>
 __device__ __forceinline__ void rep_term(const double (&xi)[D], const double* __restrict__ xj,
                                          double dip1, double djp1, double repel,
-                                         double (&out)[D]) {
+                                         double (&out)[D], bool* fixed = nullptr) {
+  static_assert(SHARED || !DETECT, "the detect-then-fix form is a shared-reciprocal form");
   double e[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) e[k] = xi[k] - xj[k];
@@ -156,10 +244,19 @@ __device__ __forceinline__ void rep_term(const double (&xi)[D], const double* __
 #pragma unroll
     for (int k = 0; k < D; ++k) out[k] = div_by_nz(e[k], rdis) * val;
 #else
-    const PairDen pd = pair_den(s);
-    const double val = div_by_nz(cij, pd.rdd);  // cij > 0 in-domain
+    if (DETECT) {
+      bool fx;
+      const PairDenNeg pn = pair_den_detect(s, fx);
+      if (fixed) *fixed = fx;
+      const double val = div_by_nz_neg(cij, pn.ndd, pn.ydd);
 #pragma unroll
-    for (int k = 0; k < D; ++k) out[k] = div_by_nz(e[k], pd.rdis) * val;
+      for (int k = 0; k < D; ++k) out[k] = div_by_nz_neg(e[k], pn.ndis, pn.yd) * val;
+    } else {
+      const PairDen pd = pair_den(s);
+      const double val = div_by_nz(cij, pd.rdd);  // cij > 0 in-domain
+#pragma unroll
+      for (int k = 0; k < D; ++k) out[k] = div_by_nz(e[k], pd.rdis) * val;
+    }
 #endif
   } else {
     const double dis = clamp_eps(sqrt(s));

@@ -150,32 +150,49 @@ __device__ __forceinline__ void col_steps(bool fast, int s0, int s1, int lane, i
 // offset from a per-block base, the same code in odd and even tiles.  No prefetch of
 // the next step's records into a second register set: the other waves of the SIMD
 // hide the LDS latency, and the kernel must stay within 120 VGPRs (see
-// faml_sym_repulse).
-template <int D, bool REPEL_ONE>
+// faml_sym_repulse).  The terms use the detect-then-fix denominators (ge_pair.hpp
+// pair_den_detect): in these tiles every row is a member and no lane meets its own
+// row, so a step takes the fix-up only for members closer than eps (a short last
+// tile's padding sits at the origin), or an all-ones low word of the distance.
+// STAMP: `fixes` counts the steps that took it.
+template <int D, bool REPEL_ONE, bool STAMP>
 __device__ __forceinline__ void tile_steps(int tt, int lane, const double* rec, double* col,
                                            const double (&xr)[D], double dr, double repel,
-                                           double (&racc)[D]) {
+                                           double (&racc)[D], int& fixes) {
   const double* rb = rec + ((64 * tt - lane) & (kSymRing - 1));
   double* cb = col + kColBase - lane;
+  // second record base for the components from 2 on: with it every record read of a
+  // step is an immediate offset (ds_read2_b64 reaches 255 slots)
+  int o2 = 2 * kRecSlots;
+  asm volatile("" : "+v"(o2));  // opaque: folded back, the offset would need the add again
+  const double* rb2 = rb + o2;
   for (int j0 = 0; j0 < 64; j0 += 8) {
     const double* rj = rb + j0;
+    const double* rj2 = rb2 + j0;
     double* cj = cb + j0;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
       double* cp = cj + jj;
       double c[D], xq[D + 1];
 #pragma unroll
-      for (int k = 0; k <= D; ++k) xq[k] = rj[k * kRecSlots + jj];
+      for (int k = 0; k <= D; ++k)
+        xq[k] = (D >= 3 && k >= 2) ? rj2[(k - 2) * kRecSlots + jj] : rj[k * kRecSlots + jj];
 #pragma unroll
       for (int k = 0; k < D; ++k) c[k] = cp[k * kColSlots];
       double t[D];
-      rep_term<D, true, REPEL_ONE>(xr, xq, dr, xq[D], repel, t);
+      bool fixed = false;
+      rep_term<D, true, REPEL_ONE, true>(xr, xq, dr, xq[D], repel, t, &fixed);
+      if (STAMP) fixes += fixed;
 #pragma unroll
       for (int k = 0; k < D; ++k) {
         racc[k] = racc[k] + t[k];
         cp[k * kColSlots] = c[k] - t[k];
       }
       step_barrier();
+      // the row's sums are taken here, step by step: with the step split into basic
+      // blocks the compiler otherwise keeps the eight steps' terms and adds them last
+#pragma unroll
+      for (int k = 0; k < D; ++k) asm volatile("" : "+v"(racc[k]));
     }
   }
 }
@@ -373,16 +390,20 @@ __device__ __forceinline__ void rows_block(int lane, int base, int s, int A, con
 // unit in queue order -- s_memrealtime (100 MHz, one clock for the whole chip)
 // when the wave took the unit, when its first column tile was handed over, when it
 // finished, the ticks spent spinning on hand-overs, HW_ID, XCC_ID, the column tiles
-// run at a raised issue priority and the hand-over waits that spun (sweep_prio).
+// run at a raised issue priority and the hand-over waits that spun (sweep_prio).  The
+// upper half of the XCC_ID word (the id is a few bits) counts the steps of tile_steps
+// in which the wave took the fix-up of pair_den_detect (round 14): the record keeps
+// its eight words.
 constexpr int kStampWords = 8;
 
 // One symmetric sweep (unit kind 0): row tile A against the columns >= 64A, the
 // column sums handed to the next sweep tile by tile.  rec / col: this wave's rings
 // (see kSymRing).  STAMP: spin ticks, the first hand-over time and the hints' census
-// (hint[0]: raised tiles, hint[1]: waits that spun).
+// (hint[0]: raised tiles, hint[1]: waits that spun, hint[2]: steps that took the
+// denominators' fix-up).
 template <int D, bool REPEL_ONE, bool STAMP>
 __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int* tprog,
-                                           int (&hint)[2],
+                                           int (&hint)[3],
                                            const double* __restrict__ X,
                                            const double* __restrict__ DP, double repel,
                                            bool repel_ok, double* __restrict__ F,
@@ -457,7 +478,7 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
       col_steps<D, REPEL_ONE, true>(fast, 64 * tt, 64 * tt + 64, lane, coff, rec, col, xr, dr,
                                     repel, racc);
     else if (fast)
-      tile_steps<D, REPEL_ONE>(tt, lane, rec, col, xr, dr, repel, racc);
+      tile_steps<D, REPEL_ONE, STAMP>(tt, lane, rec, col, xr, dr, repel, racc, hint[2]);
     else
       col_steps<D, REPEL_ONE, false>(false, 64 * tt, 64 * tt + 64, lane, coff, rec, col, xr, dr,
                                      repel, racc);
@@ -496,14 +517,15 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
 // Stamp record of one unit (STAMP builds): see kStampWords.
 __device__ __forceinline__ void stamp_unit(long long* stamps, int qi, long long t_take,
                                            long long t_first, long long spin,
-                                           const int (&hint)[2]) {
+                                           const int (&hint)[3]) {
   long long* w = stamps + (size_t)qi * kStampWords;
   w[0] = t_take;
   w[1] = t_first;
   w[2] = rt_now();
   w[3] = spin;
   w[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-  w[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
+  // XCC_ID | fix-up steps << 32
+  w[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20) | ((long long)hint[2] << 32);
   w[6] = hint[0];
   w[7] = hint[1];
 }
@@ -553,7 +575,7 @@ faml_sym_repulse(int nunits, const int4* __restrict__ units, int* __restrict__ q
     qi = __builtin_amdgcn_readfirstlane(qi);
     if (qi >= nunits) break;  // every wave leaves once the queue is drained
     long long t_take = 0, t_first = 0, spin = 0;
-    int hint[2] = {0, 0};
+    int hint[3] = {0, 0, 0};
     if (STAMP) t_take = t_first = rt_now();
     const int4 u = units[qi];
     const int A = u.y;

@@ -3,7 +3,8 @@
 Builds the C4 level-0 plan as bench.py does, runs ITERS iterations with the
 stamping kernel variant, and summarises the last launch's per-unit stamps
 (ge_sym.hpp: take / first hand-over / end / spin ticks of s_memrealtime, 100 MHz,
-HW_ID, XCC_ID, tiles run at raised issue priority, waits that spun):
+HW_ID, XCC_ID with the fix-up steps above it, tiles run at raised issue priority, waits
+that spun):
 launch span, wave occupancy over time, parked share, the tail after the queue
 drained, the critical aggregates' chains, spin and busy shares by the wave's slot on
 its SIMD (the age proxy) and the census of the priority hints.  With
@@ -123,6 +124,15 @@ def analyse(path):
                         "spun_share_by_slot": {k: float(st[(slot == int(k)) & sw, 7].sum()
                                                         / max(rem[(slot == int(k)) & sw].sum(), 1))
                                                for k in by_slot}}
+    # upper half of word 5 (XCC_ID below it): the steps of tile_steps whose wave took the
+    # fix-up of the detect-then-fix denominators (ge_pair.hpp pair_den_detect); 0 from a
+    # library before it.  Steps: 64 per column tile from the sweep's third on.
+    if st.shape[1] >= 8 and sw.any():
+        fix = st[sw, 5] >> 32
+        steps = 64 * np.maximum(rem[sw] - 2, 0)
+        out["fixup"] = {"steps_fixed": int(fix.sum()), "units_with_fixups": int((fix > 0).sum()),
+                        "tile_steps_steps": int(steps.sum()),
+                        "max_per_unit": int(fix.max())}
     return out
 
 
