@@ -251,16 +251,25 @@ fa_repulse_fast(int n, int rb, int re, const double* __restrict__ X,
   const int jbeg = jb * jchunk;
   const int jend = min(n, jbeg + jchunk);
 
+  // A vertex with a coordinate that is not finite gets NaN in every coordinate, as a
+  // row and as a partner (once per row and per staged record, not per pair): the
+  // pair's fmin drops a NaN y, so without this only the component of the bad
+  // coordinate would come out NaN and the others as finite terms clamped to 1 / eps,
+  // where the reference's NaN distance makes the whole term NaN.
   double xi[R][D], di[R], acc[R][D];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int i = base + tid + r * kFastThreads;
     const bool ok = i < re;
+    bool fin = true;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       xi[r][k] = ok ? X[(size_t)i * D + k] : 0.0;
+      fin = fin && fabs(xi[r][k]) < __builtin_inf();
       acc[r][k] = 0.0;
     }
+#pragma unroll
+    for (int k = 0; k < D; ++k) xi[r][k] = fin ? xi[r][k] : __builtin_nan("");
     di[r] = (ok ? dp1[i] : 1.0) * repel;
   }
   for (int j0 = jbeg; j0 < jend; j0 += kTileJ) {
@@ -268,8 +277,15 @@ fa_repulse_fast(int n, int rb, int re, const double* __restrict__ X,
     __syncthreads();
     if (tid < cnt) {
       const int j = j0 + tid;
+      double xj[D];
+      bool fin = true;
 #pragma unroll
-      for (int k = 0; k < D; ++k) tile[tid * W + k] = X[(size_t)j * D + k];
+      for (int k = 0; k < D; ++k) {
+        xj[k] = X[(size_t)j * D + k];
+        fin = fin && fabs(xj[k]) < __builtin_inf();
+      }
+#pragma unroll
+      for (int k = 0; k < D; ++k) tile[tid * W + k] = fin ? xj[k] : __builtin_nan("");
       tile[tid * W + D] = dp1[j];
     }
     __syncthreads();

@@ -31,7 +31,17 @@ extern "C" {
 
 #define GE_MODE_STRICT 0 /* bit-exact with the reference's serial op order */
 /* GE_MODE_FAST: re-associated / FMA / rsqrt repulsion, everything else as STRICT.
- * Single level (ge_force_atlas, ge_fa_plan_*): 1e-5 relative bar against STRICT.
+ * Single level (ge_force_atlas, ge_fa_plan_*): 1e-5 relative bar against STRICT; each
+ * repulsion sum is within (n + 16 + 24) 2^-53 sum_j |t_ij| of the exact clamped sum
+ * over the n vertices (tests/fa_fast_cases.py), deterministic, and the same bits however
+ * the rows are cut into plans.
+ * Domain of the closed-form repulsion (single level and multilevel): finite coordinates
+ * whose squared differences are finite, i.e. |x_i - x_j|^2 does not overflow
+ * (coordinates below ~1.3e154 in magnitude).  Beyond it the pair's reciprocal distance
+ * comes out NaN and is taken for a clamped pair (1 / eps), so a pair whose true force
+ * is ~0 contributes a huge one; the hot loop carries no instruction for this case.  On
+ * the single level a vertex with a NaN or infinite coordinate gives NaN in every
+ * component of every sum it takes part in (STRICT: NaN likewise for a NaN coordinate).
  * Multilevel level (ge_force_atlas_ml, ge_faml_plan_*, ge_embed and their *_dist
  * forms), dim <= 4: the streamed aggregates' repulsion runs in closed form
  * (faml_fast_repulse); resident aggregates, member rows, init, centring and radius
