@@ -2249,6 +2249,44 @@ int ge_fa_plan_repulse(ge_fa_plan* pl, const double* x, double* frep) {
   });
 }
 
+int ge_fa_plan_forces(ge_fa_plan* pl, double* d_out) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && d_out, "bad plan forces arguments");
+    ge::DeviceGuard g(pl->ctx);
+    const size_t cnt = (size_t)(pl->re - pl->rb) * pl->dim;
+    if (cnt)
+      GE_HIP(hipMemcpyAsync(d_out, pl->fprev.p, sizeof(double) * cnt, hipMemcpyDeviceToDevice,
+                            pl->ctx->stream));
+  });
+}
+
+static_assert(ge::kRowBinade == GE_ROW_BINADE && ge::kRowFlag == GE_ROW_SERIAL_FLAG &&
+                  ge::kRowBase == GE_ROW_SERIAL_BASE && ge::kRowRange == GE_ROW_SERIAL_RANGE,
+              "heavy_finish_kernel's status word is the GE_ROW_* of include/ge.h");
+
+int ge_fa_plan_rows_info(ge_fa_plan* pl, int* classes, int* heavy_rows, int* heavy_status) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && classes, "null argument");
+    ge::DeviceGuard g(pl->ctx);
+    const ge::RowClasses& rc = pl->rc;
+    const int r[6] = {rc.ntiles, rc.nheavy, rc.nmed, rc.nlight, rc.nseg, rc.seg_mode};
+    for (int k = 0; k < 6; ++k) classes[k] = r[k];
+    if (rc.nheavy == 0 || (!heavy_rows && !heavy_status)) return;
+    hipStream_t s = pl->ctx->stream;
+    if (heavy_rows)  // the row list starts with the heavy rows
+      GE_HIP(hipMemcpyAsync(heavy_rows, pl->rows.p, sizeof(int) * rc.nheavy, hipMemcpyDeviceToHost,
+                            s));
+    if (heavy_status) {
+      if (rc.nseg > 0)
+        GE_HIP(hipMemcpyAsync(heavy_status, rc.hstat, sizeof(int) * rc.nheavy,
+                              hipMemcpyDeviceToHost, s));
+      else  // whole rows (classed_rows_kernel): always the ordered sum
+        for (int h = 0; h < rc.nheavy; ++h) heavy_status[h] = GE_ROW_SERIAL_WHOLE;
+    }
+    GE_HIP(hipStreamSynchronize(s));
+  });
+}
+
 int ge_fa_plan_far_info(ge_fa_plan* pl, int* active, int* reason, double* theta, int* item_rows,
                         int* levels, int* level_cells, long long* level_points, int* fallback,
                         long long* accepted, long long* exact_leaves, long long* pair_terms,

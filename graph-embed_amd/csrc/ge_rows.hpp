@@ -64,6 +64,7 @@ struct RowClasses {
   const int* seg = nullptr;       // nseg x {heavy row slot, first, last entry offset in the row}
   long long* hacc = nullptr;      // nheavy x D x {S, A}: binade sums of the segments (zeroed)
   int* hflag = nullptr;           // nheavy: a segment could not use the binade sum
+  int* hstat = nullptr;           // nheavy: how the last pass finished the row (kRow*)
   double* hterm = nullptr;        // kSegStore: the heavy rows' terms, row h at hoff[h], dim-major
   const long long* hoff = nullptr;
   int seg_mode = 0;               // kSegBinade / kSegStore when nseg > 0
@@ -527,10 +528,15 @@ __device__ __forceinline__ void segment_rows(const RowClasses& L, const P& p, in
   if (tid == 0 && (rflag[0] | rflag[1] | rflag[2] | rflag[3])) atomicOr(L.hflag + h, 1);
 }
 
+// How heavy_finish_kernel finished a heavy row (RowClasses::hstat; GE_ROW_* in
+// include/ge.h): the binade sum, or the serial sum with every test that failed.
+constexpr int kRowBinade = 1, kRowFlag = 2, kRowBase = 4, kRowRange = 8;
+
 // After every segment: one wave per heavy row turns its binade sums into the
 // row's force (or, when they do not apply, adds its terms serially in stored
 // order), then gravity and the update; the accumulators are zeroed for the
-// next pass.
+// next pass, and the row's status word says which way it went and why
+// (ge_fa_plan_rows_info; one plain store by the lane that clears the flag).
 template <int D, class P>
 __global__ void __launch_bounds__(kRowT) heavy_finish_kernel(RowClasses L, P p) {
   __shared__ __attribute__((aligned(16))) double buf[4 * 64 * D];
@@ -540,14 +546,18 @@ __global__ void __launch_bounds__(kRowT) heavy_finish_kernel(RowClasses L, P p) 
   typename P::State st;
   p.load(L.rows[h], st);
   long long* acc = L.hacc + (size_t)h * 2 * D;
-  bool ok = L.hflag[h] == 0;
+  // every test of every dimension, so that the status names all that failed (a base
+  // that is not normal has no range test; its segments raised the flag as well)
+  int why = L.hflag[h] == 0 ? 0 : kRowFlag;
   double sum[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) {
     int uexp;
     long long P0;
-    ok = ok && binade_base(st.acc[k], uexp, P0) && binade_result(P0, uexp, acc[2 * k], acc[2 * k + 1], sum[k]);
+    if (!binade_base(st.acc[k], uexp, P0)) why |= kRowBase;
+    else if (!binade_result(P0, uexp, acc[2 * k], acc[2 * k + 1], sum[k])) why |= kRowRange;
   }
+  const bool ok = why == 0;
   if (ok) {
 #pragma unroll
     for (int k = 0; k < D; ++k) st.acc[k] = sum[k];
@@ -558,7 +568,10 @@ __global__ void __launch_bounds__(kRowT) heavy_finish_kernel(RowClasses L, P p) 
   p.finish(st, lane == 0);
   wave_lds_sync();  // every lane has read the accumulators
   if (lane < 2 * D) acc[lane] = 0;
-  if (lane == 0) L.hflag[h] = 0;
+  if (lane == 0) {
+    L.hflag[h] = 0;
+    L.hstat[h] = ok ? kRowBinade : why;
+  }
 }
 
 // kSegStore, phase A: the terms of one segment of a heavy row, stored
@@ -709,7 +722,7 @@ __global__ void __launch_bounds__(kRowT, GE_ROWS_MINBLOCKS) classed_rows_kernel(
 // beside the tiles, and the heavy rows' binade accumulators (segment mode).
 struct RowStreams {
   DevBuf<long long> hacc, hoff;
-  DevBuf<int> hflag;
+  DevBuf<int> hflag, hstat;
   DevBuf<double> hterm;
   int nheavy = 0;
   // allocate (and zero) the heavy rows' segment buffers; deg: their entry
@@ -730,9 +743,12 @@ struct RowStreams {
     hacc.alloc((size_t)rc.nheavy * 2 * D);
     hflag.alloc(rc.nheavy);
     GE_HIP(hipMemsetAsync(hacc.p, 0, sizeof(long long) * hacc.n, s));
+    hstat.alloc(rc.nheavy);
     GE_HIP(hipMemsetAsync(hflag.p, 0, sizeof(int) * hflag.n, s));
+    GE_HIP(hipMemsetAsync(hstat.p, 0, sizeof(int) * hstat.n, s));
     rc.hacc = hacc.p;
     rc.hflag = hflag.p;
+    rc.hstat = hstat.p;
     nheavy = rc.nheavy;
   }
   hipStream_t side = nullptr;

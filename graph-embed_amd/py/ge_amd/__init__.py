@@ -34,6 +34,9 @@ MODE_FARFIELD = 2
 FAR_MAX_LEVELS = 8  # GE_FAR_MAX_LEVELS
 # ge_fa_plan_far_info reason codes (GE_FAR_*)
 FAR_REASONS = ("active", "not_requested", "dim", "row_shard", "mass", "small")
+# GE_ROW_*: how the last row pass finished a heavy row (FaPlan.rows_info)
+ROW_NONE, ROW_BINADE, ROW_SERIAL_FLAG, ROW_SERIAL_BASE, ROW_SERIAL_RANGE, ROW_SERIAL_WHOLE = (
+    0, 1, 2, 4, 8, 16)
 MATH_OPS = {"sqrt": 0, "div": 1, "pair": 2, "rep": 3}  # GE_MATH_*
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -71,6 +74,8 @@ _SIGS = {
     "ge_fa_plan_step": (ctypes.c_int, [_vp, _vp, _vp]),
     "ge_fa_plan_attract": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "ge_fa_plan_repulse": (ctypes.c_int, [_vp, _vp, _vp]),
+    "ge_fa_plan_forces": (ctypes.c_int, [_vp, _vp]),
+    "ge_fa_plan_rows_info": (ctypes.c_int, [_vp, _ip, _vp, _vp]),
     "ge_fa_plan_far_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_double), _ip, _ip,
                                            _ip, ctypes.POINTER(ctypes.c_longlong), _ip,
                                            ctypes.POINTER(ctypes.c_longlong),
@@ -719,6 +724,27 @@ class FaPlan:
         """One repulsion pass alone on the coordinates d_x (n * dim) into d_frep (the
         plan's rows * dim), in the plan's mode (ge_fa_plan_repulse)."""
         _check(lib().ge_fa_plan_repulse(self.h, _vp(d_x), _vp(d_frep)))
+
+    def forces(self, d_out):
+        """Copies the forces of the last step or attract ((row_end - row_begin) * dim
+        doubles) to the device buffer d_out on the plan's stream (ge_fa_plan_forces)."""
+        _check(lib().ge_fa_plan_forces(self.h, _vp(d_out)))
+
+    def rows_info(self):
+        """ge_fa_plan_rows_info: ntiles, nheavy, nmed, nlight, nseg, seg_mode of the plan's
+        rows; heavy_rows (their ids, longest first) and heavy_status (how the last row
+        pass finished each: ROW_BINADE, or'ed ROW_SERIAL_FLAG / _BASE / _RANGE,
+        ROW_SERIAL_WHOLE, or ROW_NONE before any pass)."""
+        cls = (ctypes.c_int * 6)()
+        _check(lib().ge_fa_plan_rows_info(self.h, cls, None, None))
+        out = dict(zip(("ntiles", "nheavy", "nmed", "nlight", "nseg", "seg_mode"), cls))
+        rows = np.empty(out["nheavy"], dtype=np.int32)
+        stat = np.empty(out["nheavy"], dtype=np.int32)
+        if out["nheavy"]:
+            _check(lib().ge_fa_plan_rows_info(self.h, cls, rows.ctypes.data_as(_vp),
+                                              stat.ctypes.data_as(_vp)))
+        out["heavy_rows"], out["heavy_status"] = rows, stat
+        return out
 
     def far_info(self):
         """ge_fa_plan_far_info: active, reason (FAR_REASONS), theta, item_rows, levels,

@@ -175,6 +175,37 @@ int ge_fa_plan_kernel_ms(ge_fa_plan* plan, double* repulsion_ms, double* attract
  * STRICT step has no separate repulsion: there the ordered-pair kernels run, with the
  * same bits).  The single-level twin of ge_faml_plan_repulse; it synchronises. */
 int ge_fa_plan_repulse(ge_fa_plan* plan, const double* d_x, double* d_frep);
+/* The forces of the last ge_fa_plan_step or ge_fa_plan_attract -- what the reference's
+ * force holds after gravity (include/forceatlas.hpp:205-211), the value the next
+ * iteration's swing reads -- copied to d_out ((row_end - row_begin)*dim doubles, device)
+ * on the plan's stream; zeros before the first pass.  Read only; it does not
+ * synchronise. */
+int ge_fa_plan_forces(ge_fa_plan* plan, double* d_out);
+/* The classes of the plan's CSR rows (graph-embed_amd/csrc/ge_rows.hpp) and how the last
+ * pass finished each heavy row.  classes[6]: tiles, heavy rows, medium rows, light rows,
+ * heavy-row segments, segment mode (0 whole rows, 1 binade sums).  heavy_rows and
+ * heavy_status (host, classes[1] ints each, either may be NULL; call once with both NULL
+ * for the count): the heavy rows' ids in the plan's order (longest first) and, of the
+ * last row pass (the attraction pass of ge_fa_plan_step where it runs the row kernels,
+ * or ge_fa_plan_attract), one of
+ *   GE_ROW_NONE          no row pass has run on the plan;
+ *   GE_ROW_BINADE        the segments' integer sums gave the force;
+ *   GE_ROW_SERIAL_*      the terms were added in stored order, because (or'ed; every
+ *                        test of every dimension is made) FLAG a segment met a tie, a
+ *                        term of 2^36 units or more, a non-finite term or a base that is
+ *                        not normal; BASE a dimension's repulsion sum is zero, subnormal
+ *                        or not finite; RANGE a dimension's prefixes are not known to
+ *                        stay strictly inside the base's binade;
+ *   GE_ROW_SERIAL_WHOLE  the plan keeps heavy rows whole (segment mode 0): always the
+ *                        ordered sum.
+ * Diagnostics; the results do not depend on it.  Synchronises. */
+#define GE_ROW_NONE 0
+#define GE_ROW_BINADE 1
+#define GE_ROW_SERIAL_FLAG 2
+#define GE_ROW_SERIAL_BASE 4
+#define GE_ROW_SERIAL_RANGE 8
+#define GE_ROW_SERIAL_WHOLE 16
+int ge_fa_plan_rows_info(ge_fa_plan* plan, int* classes, int* heavy_rows, int* heavy_status);
 /* GE_MODE_FARFIELD diagnostics.  active: the far field runs; reason: why not
  * (GE_FAR_*).  theta, rows per work item, the levels of the hierarchy (0 = leaves)
  * with each level's cell count and cell size in points (arrays of GE_FAR_MAX_LEVELS).

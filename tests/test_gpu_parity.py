@@ -72,7 +72,7 @@ def test_fa_tiled_kernel_bitexact(ctx, oracle, n, dim):
 def test_fa_degree_classes(ctx, oracle, monkeypatch, use_weights, tiles):
     """Rows of every degree class of the attraction kernel (ge_rows.hpp): light,
     wave-per-row (> 32 edges) and block-per-row (> 2048 edges, several chunks);
-    with GE_ROWS_TILES=1 the tiles (<= 1024 entries) and block-per-row beyond."""
+    with GE_ROWS_TILES=1 the tiles (<= 512 entries) and block-per-row beyond."""
     monkeypatch.setenv("GE_STREAM_MAX", "0")  # the large-level kernels
     monkeypatch.setenv("GE_ROWS_TILES", tiles)
     A = G.with_hubs(G.rmat(6000, 30000, seed=11), [(5, 4500), (17, 2100), (900, 300)])
@@ -88,16 +88,19 @@ def test_fa_degree_classes(ctx, oracle, monkeypatch, use_weights, tiles):
 @pytest.mark.parametrize("segments", ["1", "0"])
 @pytest.mark.parametrize("dim", [1, 2, 3, 4])
 def test_fa_row_tiles(ctx, oracle, monkeypatch, dim, segments):
-    """Tiled CSR rows: rows at and around the tile capacity (tile vs heavy),
-    tiles closed by the row limit and by the entry limit, isolated rows, every
+    """Tiled CSR rows: rows at and around the tile capacity of 512 entries (511 and 512
+    in a tile, 513 heavy) and at 1023 | 1024 | 1025 (the second | third segment of a heavy
+    row), tiles closed by the row limit and by the entry limit, isolated rows, every
     dimension; heavy rows as binade-sum segments or whole rows (GE_ROWS_SEGMENTS)."""
     monkeypatch.setenv("GE_STREAM_MAX", "0")  # the large-level kernels
     monkeypatch.setenv("GE_ROWS_TILES", "1")
     monkeypatch.setenv("GE_ROWS_SEGMENTS", segments)
     A = G.with_degrees(G.rmat(5000, 20000, seed=dim), {7: 1023, 8: 1024, 9: 1025, 300: 700,
-                                                       301: 400, 4000: 1500}, seed=dim)
+                                                       301: 400, 4000: 1500, 2000: 511,
+                                                       2001: 512, 2002: 513}, seed=dim)
     deg = np.diff(A[0])
     assert list(deg[[7, 8, 9, 300]]) == [1023, 1024, 1025, 700] and (deg == 0).any()
+    assert list(deg[[2000, 2001, 2002]]) == [511, 512, 513]
     X0 = G.random_coords(len(deg), dim, seed=dim)
     want = oracle.force_atlas(A, dim, coords=X0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=3), want)
