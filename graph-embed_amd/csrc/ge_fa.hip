@@ -1492,13 +1492,6 @@ constexpr int kRowsPerThreadFast = 4;
 constexpr int kFarMinDefault = 131072;
 constexpr int kFarItemRows = 64;
 
-int device_cus() {
-  int dev = 0, cus = 0;
-  GE_HIP(hipGetDevice(&dev));
-  GE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  return cus > 0 ? cus : 256;
-}
-
 // Lanes per row of the small-level kernels.
 inline int grouped_lanes(int rows) {
   int G = 1;  // lanes per row: aim for >= 128 K lanes, at most one wave per row
@@ -1716,8 +1709,7 @@ struct ge_fa_plan {
   int cus = 256;
   bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
   bool profiling = false;
-  std::vector<hipEvent_t> events;  // 3 per timed step
-  size_t next_event = 0;
+  ge::EventPool events{3 * 64};  // 3 per timed step
   // Symmetric repulsion (ge_sym.hpp) for a whole large level in STRICT mode: the n
   // vertices as one "aggregate" of T = ceil(n / 64) row tiles, every unordered pair
   // evaluated once.  ctl = {queue, prog[T]}, zeroed before every launch.
@@ -1734,7 +1726,6 @@ struct ge_fa_plan {
   int far_reason = GE_FAR_NOT_REQUESTED;
   ~ge_fa_plan() {
     ge::far_destroy(far);
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
     if (sym_err_h) (void)hipHostFree(sym_err_h);
   }
 };
@@ -1875,19 +1866,8 @@ static void plan_repulse_into(ge_fa_plan* pl, hipStream_t s, const double* xc, d
 
 static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
   hipStream_t s = pl->ctx->stream;
-  hipEvent_t* ev = nullptr;
-  if (pl->profiling) {
-    if (pl->next_event + 3 > pl->events.size()) {
-      for (int k = 0; k < 3 * 64; ++k) {
-        hipEvent_t e;
-        GE_HIP(hipEventCreate(&e));
-        pl->events.push_back(e);
-      }
-    }
-    ev = &pl->events[pl->next_event];
-    pl->next_event += 3;
-    GE_HIP(hipEventRecord(ev[0], s));
-  }
+  hipEvent_t* ev = pl->profiling ? pl->events.take(3) : nullptr;
+  if (ev) GE_HIP(hipEventRecord(ev[0], s));
   dispatch_dim(pl->dim, [&](auto Dc) {
     constexpr int D = decltype(Dc)::value;
     if (pl->p.mode == GE_MODE_STRICT && pl->n <= stream_max() && !std::getenv("GE_GRP_SPLIT")) {
@@ -1909,17 +1889,8 @@ static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
 // (profiling: the repulsion interval is empty).
 static void plan_attract(ge_fa_plan* pl, const double* xc, const double* frep, double* xn) {
   hipStream_t s = pl->ctx->stream;
-  hipEvent_t* ev = nullptr;
-  if (pl->profiling) {
-    if (pl->next_event + 3 > pl->events.size()) {
-      for (int k = 0; k < 3 * 64; ++k) {
-        hipEvent_t e;
-        GE_HIP(hipEventCreate(&e));
-        pl->events.push_back(e);
-      }
-    }
-    ev = &pl->events[pl->next_event];
-    pl->next_event += 3;
+  hipEvent_t* ev = pl->profiling ? pl->events.take(3) : nullptr;
+  if (ev) {
     GE_HIP(hipEventRecord(ev[0], s));
     GE_HIP(hipEventRecord(ev[1], s));
   }
@@ -2331,7 +2302,7 @@ int ge_fa_plan_set_profiling(ge_fa_plan* pl, int enable) {
   return ge::guarded([&] {
     GE_REQUIRE(pl, "null plan");
     pl->profiling = enable != 0;
-    pl->next_event = 0;
+    pl->events.reset();
   });
 }
 
@@ -2341,19 +2312,8 @@ int ge_fa_plan_kernel_ms(ge_fa_plan* pl, double* rep_ms, double* attr_ms, int* l
     ge::DeviceGuard g(pl->ctx);
     GE_HIP(hipStreamSynchronize(pl->ctx->stream));
     ge::sym_check(pl);
-    double a = 0.0, b = 0.0;
-    int cnt = 0;
-    for (size_t k = 0; k + 3 <= pl->next_event; k += 3) {
-      float t1 = 0.f, t2 = 0.f;
-      GE_HIP(hipEventElapsedTime(&t1, pl->events[k], pl->events[k + 1]));
-      GE_HIP(hipEventElapsedTime(&t2, pl->events[k + 1], pl->events[k + 2]));
-      a += t1;
-      b += t2;
-      ++cnt;
-    }
-    *rep_ms = cnt ? a / cnt : 0.0;
-    *attr_ms = cnt ? b / cnt : 0.0;
-    *launches = cnt;
+    *rep_ms = pl->events.mean_ms(3, 0, 1, launches);
+    *attr_ms = pl->events.mean_ms(3, 1, 2);
   });
 }
 

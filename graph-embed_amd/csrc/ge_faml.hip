@@ -32,14 +32,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <numeric>
 #include <queue>
 #include <string>
 #include <vector>
 
+#include "ge_faml_sched.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
 #include "ge_rows.hpp"
@@ -331,7 +334,6 @@ faml_resident(const int* __restrict__ order, const int* __restrict__ pack_beg,
 
 constexpr int kHT = 256;   // threads per block of the streamed kernels
 constexpr int kBigW = 64;  // records per wave tile
-constexpr int kBigDefaultR = 1, kBigDefaultU = 1;
 
 template <int D>
 __global__ void __launch_bounds__(kHT)
@@ -767,28 +769,15 @@ __global__ void pos_of_kernel(int N, const int* __restrict__ pt_ix, int* __restr
   if (c < N) pos_of[pt_ix[c]] = c;
 }
 
-// Greedy packs over `ids` (already size-sorted) with total members <= cap.
-void build_packs(const std::vector<int>& ids, const int* h_pt_ip, int cap, int max_aggs,
-                 std::vector<int>& order, std::vector<int>& beg) {
-  beg.push_back((int)order.size());
-  int tot = 0, cnt = 0;
-  for (int a : ids) {
-    const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-    if (cnt > 0 && (tot + s > cap || cnt >= max_aggs)) {
-      beg.push_back((int)order.size());
-      tot = 0;
-      cnt = 0;
-    }
-    order.push_back(a);
-    tot += s;
-    ++cnt;
-  }
-  if (cnt > 0) beg.push_back((int)order.size());
-}
-
-// Streamed repulsion variants: row slots R x partners in flight U.
-#define GE_BIG_VARIANTS(X) X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(4, 1)
-constexpr int big_code(int R, int U) { return R * 8 + U; }
+// The schedule (ge_faml_sched.hpp) restates what the kernels fix and lays its tables
+// out as the kernels read them.
+static_assert(kSchedFastR == kFastR && kSchedSymWaves == kSymT / 64 &&
+                  kSchedSweep == kUnitSweep && kSchedRows == kUnitRows,
+              "the schedule's constants are the kernels'");
+static_assert(sizeof(SchedInt2) == sizeof(int2) && alignof(SchedInt2) <= alignof(int2) &&
+                  sizeof(SchedInt4) == sizeof(int4) && alignof(SchedInt4) <= alignof(int4) &&
+                  offsetof(SchedInt4, w) == offsetof(int4, w),
+              "schedule items and units are uploaded as int2 / int4");
 
 template <int D>  // the variants of D <= kNarrowMaxDim (below)
 void launch_big_repulse_narrow(int code, int blocks, hipStream_t st, int nitems,
@@ -888,7 +877,7 @@ struct ge_faml_plan {
   long long sym_limit = 0;  // that wait's bound in ticks of the device wall clock
   int nunits = 0, ntiles = 0, sym_blocks = 0;
   int rows_mode = 0, swept = 0;  // streamed aggregates by schedule (ge_sym.hpp)
-  std::vector<int4> h_units;          // host copy of `units` (timeline dumps)
+  std::vector<ge::SchedInt4> h_units;  // host copy of `units` (timeline dumps)
   ge::DevBuf<long long> stamps;       // GE_SYM_STAMPS: per-unit timeline of the last launch
   std::string stamp_path;
   double streamed_pairs = 0.0;
@@ -898,12 +887,9 @@ struct ge_faml_plan {
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
   bool profiling = false;
-  std::vector<hipEvent_t> ev;  // 4 per timed run: start, resident end, streamed start/end
-  size_t next_ev = 0;
-  std::vector<hipEvent_t> rev;  // 2 per profiled repulsion launch
-  size_t next_rev = 0;
-  std::vector<hipEvent_t> aev;  // 2 per profiled member-row pass (FamlRows)
-  size_t next_aev = 0;
+  ge::EventPool ev{64};    // 4 per timed run: start, resident end, streamed start/end
+  ge::EventPool rev{256};  // 2 per profiled repulsion launch
+  ge::EventPool aev{256};  // 2 per profiled member-row pass (FamlRows)
   long long streamed_entries = 0;  // CSR entries of the streamed members' rows
   // aggregates split by row tiles across the ranks of `comm`: this
   // rank computes its rows' forces and updates, and the split aggregates' rows are
@@ -919,352 +905,117 @@ struct ge_faml_plan {
 
 namespace ge {
 
+// blocks per CU of faml_sym_repulse<dim> (1 where the sweeps are not compiled)
+static int sym_occupancy(int dim) {
+  int occ = 1;
+  if (dim > kNarrowMaxDim) return occ;
+  dispatch_dim_narrow(dim, [&](auto Dc) {
+    constexpr int D = decltype(Dc)::value;
+    GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &occ, (const void*)faml_sym_repulse<D, false>, kSymT, 0));
+  });
+  return occ;
+}
+
+// The scheduler's inputs: the caller's lists and device figures, with what the
+// dimension and the environment settle.
+static FamlSchedIn faml_sched_in(const int* h_pt_ip, const std::vector<int>& aggs,
+                                 const std::vector<int>& split, int rank, int nranks, int dim,
+                                 int mode, int cus, int sym_occ) {
+  FamlSchedIn in;
+  in.pt_ip = h_pt_ip;
+  in.aggs = &aggs;
+  in.split = &split;
+  in.rank = rank;
+  in.nranks = nranks;
+  in.dim = dim;
+  in.mode = mode;
+  in.large_cap = large_cap(dim);
+  in.wide = wide_dim(dim);
+  in.cus = cus;
+  in.sym_occ = sym_occ;
+  in.knobs = faml_knobs_from_env();
+  return in;
+}
+
 // aggs: the aggregates this plan runs (strictly increasing ids).
 // split: aggregates whose row tiles are dealt over the ranks of pl->comm (the
 // same list on every rank; tiles [T r / N, T (r + 1) / N) to rank r).
+// The schedule is faml_schedule's (ge_faml_sched.hpp); this is its device part.
 static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vector<int>& aggs,
-                            const std::vector<int>& split_aggs = std::vector<int>()) {
-  const std::vector<int>& split = split_aggs;
+                            const std::vector<int>& split = std::vector<int>()) {
   hipStream_t st = pl->ctx->stream;
-  const int dim = pl->dim;
-  // Work of aggregate a per iteration ~ s^2.  Aggregates whose share would
-  // keep one CU busy for more than a quarter of the per-CU average go to the
-  // streamed path (many blocks per aggregate, one launch per iteration);
-  // the rest stay resident in LDS for all iterations.
-  double W = 0.0;
-  for (int a : aggs) {
-    const double s = h_pt_ip[a + 1] - h_pt_ip[a];
-    W += s * s;
-  }
-  int dev = 0, cus = 256;
-  GE_HIP(hipGetDevice(&dev));
-  GE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const double per_cu = W / std::max(cus, 1);
-  int res_cap = (int)std::sqrt(per_cu / 4.0);  // largest aggregate kept resident
-  // GE_FAML_RES_CAP: the cap itself (tests: the large-resident class on small inputs)
-  if (const char* e = std::getenv("GE_FAML_RES_CAP")) res_cap = std::atoi(e);
-  res_cap = std::max(256, std::min(res_cap, large_cap(dim)));
-  pl->res_cap = res_cap;
-
-  std::vector<int> small, mid, large, big;
-  for (int a : aggs) {
-    const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-    if (s <= 0) continue;
-    if (s <= 64) small.push_back(a);
-    else if (s <= 256) mid.push_back(a);
-    else if (s <= res_cap) large.push_back(a);
-    else big.push_back(a);
-  }
-  pl->census[0] = (int)small.size();
-  pl->census[1] = (int)mid.size();
-  pl->census[2] = (int)large.size();
-  pl->census[3] = (int)big.size() + (int)split.size();
-  auto by_size = [&](int x, int y) {
-    const int sx = h_pt_ip[x + 1] - h_pt_ip[x], sy = h_pt_ip[y + 1] - h_pt_ip[y];
-    return sx != sy ? sx > sy : x < y;
-  };
-  std::sort(small.begin(), small.end(), by_size);
-  std::sort(mid.begin(), mid.end(), by_size);
-  std::sort(large.begin(), large.end(), by_size);
-  std::sort(big.begin(), big.end(), by_size);
-
-  std::vector<int> order, beg_s, beg_m, beg_l;
-  build_packs(small, h_pt_ip, 64, 64, order, beg_s);
-  build_packs(mid, h_pt_ip, 256, 256, order, beg_m);
-  build_packs(large, h_pt_ip, large_cap(dim), 1, order, beg_l);
-  // streamed members and their repulsion work items (aggregate, first row):
-  // R row slots of 64 per wave, taken in descending-work order
-  std::vector<int> rows;
-  for (int a : big)
-    for (int li = 0; li < h_pt_ip[a + 1] - h_pt_ip[a]; ++li) rows.push_back(h_pt_ip[a] + li);
-  // split aggregates: this rank's row tiles are streamed rows like the others; every
-  // member is initialised and given its internal degree (all are columns)
-  const int rank = pl->comm ? pl->comm->rank : 0, nranks = pl->comm ? pl->comm->nranks : 1;
-  auto tiles_of = [&](int a, int r, int& t0, int& t1) {
-    const long long T = (h_pt_ip[a + 1] - h_pt_ip[a] + 63) / 64;
-    t0 = (int)(T * r / nranks);
-    t1 = (int)(T * (r + 1) / nranks);
-  };
-  std::vector<int> irows = rows;
-  std::vector<int> xr, xcounts(nranks, 0);
-  for (int r = 0; r < nranks; ++r)
-    for (int a : split) {
-      const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-      int t0, t1;
-      tiles_of(a, r, t0, t1);
-      for (int li = 64 * t0; li < std::min(s, 64 * t1); ++li) {
-        const int c = h_pt_ip[a] + li;
-        if (r == rank) rows.push_back(c);
-        irows.push_back(c);
-        xr.push_back(c);
-        ++xcounts[r];
-      }
-    }
-  // row slots x partners in flight (GE_FAML_R / GE_FAML_U override; only the
-  // compiled variants of GE_BIG_VARIANTS are accepted)
-  int R = kBigDefaultR, U = kBigDefaultU;
-  if (const char* e = std::getenv("GE_FAML_R")) R = std::atoi(e);
-  if (const char* e = std::getenv("GE_FAML_U")) U = std::atoi(e);
-  bool known = false;
-#define GE_BIG_KNOWN(RR, UU) known = known || (R == RR && U == UU);
-  GE_BIG_VARIANTS(GE_BIG_KNOWN)
-#undef GE_BIG_KNOWN
-  // the wide schedule (ge_pair.hpp) has the one variant, and no symmetric sweeps
-  const bool wide = pl->wide = wide_dim(dim);
-  if (!known || wide) {
-    R = kBigDefaultR;
-    U = kBigDefaultU;
-  }
-  std::vector<int> erows;
-  if (!rows.empty()) {  // degree classes of the streamed members' CSR rows
-    std::vector<int> h_ip(pl->n + 1), h_ptix(pl->n);
-    GE_HIP(hipMemcpyAsync(h_ip.data(), pl->ip, sizeof(int) * (pl->n + 1), hipMemcpyDeviceToHost, st));
-    GE_HIP(hipMemcpyAsync(h_ptix.data(), pl->pt_ix, sizeof(int) * pl->n, hipMemcpyDeviceToHost,
-                          st));
+  const int dim = pl->dim, n = pl->n;
+  const int cus = device_cus();
+  const int nranks = pl->comm ? pl->comm->nranks : 1;
+  const FamlSched s = faml_schedule(faml_sched_in(h_pt_ip, aggs, split,
+                                                  pl->comm ? pl->comm->rank : 0, nranks, dim,
+                                                  pl->mode, cus, sym_occupancy(dim)));
+  pl->res_cap = s.res_cap;
+  std::copy(s.census, s.census + 4, pl->census);
+  pl->off_m = s.off_m;
+  pl->off_l = s.off_l;
+  pl->ns = s.ns;
+  pl->nm = s.nm;
+  pl->nl = s.nl;
+  pl->nrows = (int)s.rows.size();
+  pl->nirows = (int)s.irows.size();
+  pl->nitems = (int)s.items.size();
+  pl->nhuge = (int)s.huge.size();
+  pl->R = s.R;
+  pl->code = s.code;
+  pl->wide = s.wide;
+  pl->fast = s.fast;
+  pl->nfitems = (int)s.fitems.size();
+  pl->sym = s.sym;
+  pl->nunits = (int)s.units.size();
+  pl->ntiles = s.ntiles;
+  pl->sym_blocks = s.sym_blocks;
+  pl->rows_mode = s.rows_mode;
+  pl->swept = s.swept;
+  pl->streamed_pairs = s.streamed_pairs;
+  if (!s.rows.empty()) {  // degree classes of the streamed members' CSR rows
+    std::vector<int> h_ip(n + 1), h_ptix(n), erows;
+    GE_HIP(hipMemcpyAsync(h_ip.data(), pl->ip, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, st));
+    GE_HIP(hipMemcpyAsync(h_ptix.data(), pl->pt_ix, sizeof(int) * n, hipMemcpyDeviceToHost, st));
     GE_HIP(hipStreamSynchronize(st));
-    std::vector<int> deg(rows.size());
-    for (size_t q = 0; q < rows.size(); ++q) {
-      const int v = h_ptix[rows[q]];
+    std::vector<int> deg(s.rows.size());
+    for (size_t q = 0; q < s.rows.size(); ++q) {
+      const int v = h_ptix[s.rows[q]];
       deg[q] = h_ip[v + 1] - h_ip[v];
       pl->streamed_entries += deg[q];
     }
     // the in-aggregate repulsion is not far above the external pulls (measured
     // at C3: every heavy row left the binade), so heavy rows store their terms
     std::vector<int> hdeg;
-    classify_rows(rows, deg, erows, pl->ecls, kSegStore, &hdeg);
-    pl->ecode.alloc(std::max(h_ip[pl->n], 1));
+    classify_rows(s.rows, deg, erows, pl->ecls, kSegStore, &hdeg);
+    pl->ecode.alloc(std::max(h_ip[n], 1));
     pl->erows.alloc(erows.size());
     pl->erows.upload(erows.data(), erows.size(), st);
     pl->ecls.bind(pl->erows.p);
-    pl->rstreams.attach(pl->ecls, pl->dim, st, hdeg);
+    pl->rstreams.attach(pl->ecls, dim, st, hdeg);
   }
-  // split tiles are one-row-slot items (R = 1): settle R before any item is built,
-  // so the whole-aggregate items step by the R the kernel is launched with
-  for (int a : split) {
-    int t0, t1;
-    tiles_of(a, rank, t0, t1);
-    if (t1 > t0) R = 1;
-  }
-  struct Item { int a, r0; double work; };
-  std::vector<Item> its;
-  for (int a : big) {
-    const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-    for (int r0 = 0; r0 < s; r0 += 64 * R)
-      its.push_back({a, r0, (double)std::min(R, (s - r0 + 63) / 64) * s});
-  }
-  for (int a : split) {  // this rank's tiles, one item each (R = 1 rows per slot)
-    const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-    int t0, t1;
-    tiles_of(a, rank, t0, t1);
-    for (int t = t0; t < t1; ++t) its.push_back({a, 64 * t, (double)s});
-  }
-  std::stable_sort(its.begin(), its.end(),
-                   [](const Item& x, const Item& y) { return x.work > y.work; });
-  std::vector<int2> items;
-  for (const Item& it : its) items.push_back(make_int2(it.a, it.r0));
-  // FAST mode: row items of up to kFastR 64-row tiles, whole aggregates and this rank's
-  // tiles of the split ones alike (a row's sum does not depend on the item it is in);
-  // the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) do not apply
-  std::vector<int4> fitems;
-  if (pl->mode == GE_MODE_FAST && !wide) {
-    struct FItem { int a, r0, r1; double work; };
-    std::vector<FItem> fi;
-    auto cut = [&](int a, int b0, int b1) {  // rows [b0, b1) of aggregate a
-      const int s = h_pt_ip[a + 1] - h_pt_ip[a];
-      for (int r0 = b0; r0 < b1; r0 += 64 * kFastR) {
-        const int r1 = std::min(b1, r0 + 64 * kFastR);
-        fi.push_back({a, r0, r1, (double)((r1 - r0 + 63) / 64) * s});
-      }
-    };
-    for (int a : big) cut(a, 0, h_pt_ip[a + 1] - h_pt_ip[a]);
-    for (int a : split) {
-      int t0, t1;
-      tiles_of(a, rank, t0, t1);
-      cut(a, 64 * t0, std::min(h_pt_ip[a + 1] - h_pt_ip[a], 64 * t1));
-    }
-    std::stable_sort(fi.begin(), fi.end(),
-                     [](const FItem& x, const FItem& y) { return x.work > y.work; });
-    for (const FItem& f : fi) fitems.push_back(make_int4(f.a, f.r0, f.r1, 0));
-  }
-  pl->fast = !fitems.empty();
-  pl->nfitems = (int)fitems.size();
-  // symmetric sweeps: one unit per (aggregate, row tile), in the order of their
-  // earliest start (2A tile-times into the aggregate), larger aggregates first
-  {
-    const char* e = std::getenv("GE_FAML_SYM");
-    pl->sym = !(e && *e == '0') && !wide && !pl->fast;
-  }
-  if (pl->sym && (!big.empty() || !split.empty())) {
-    // The sweeps of an aggregate with T row tiles form a chain of ~2.5 T tile-times
-    // (each sweep starts after its predecessor has passed its first two tiles); the
-    // launch takes about (sum of T^2 / 2 sweep tiles) / (resident waves).  While the
-    // longest chain exceeds that, the largest aggregate runs as plain row blocks
-    // (every ordered pair, ~0.8 the step cost of a sweep, no chain).
-    std::vector<int> T(big.size());
-    const bool any_big = !big.empty();
-    for (size_t b = 0; b < big.size(); ++b) T[b] = (h_pt_ip[big[b] + 1] - h_pt_ip[big[b]] + 63) / 64;
-    int occ = 1;
-    dispatch_dim_narrow(dim, [&](auto Dc) {
-      constexpr int D = decltype(Dc)::value;
-      GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &occ, (const void*)faml_sym_repulse<D, false>, kSymT, 0));
-    });
-    // three blocks (waves) per SIMD of the four that fit: fewer units in flight spin
-    // less on hand-overs (C4 N = 1: 137.2 against 138.3 ms per launch; N = 8 shares
-    // 30.0 against 32.7 ms; scripts/sym_timeline.py, profiles/r03/sym_timeline)
-    const int bpc = std::min(std::max(occ, 1), 3);
-    pl->sym_blocks = cus * bpc;
-    const double waves = (double)pl->sym_blocks * (kSymT / 64);
-    // Per streamed aggregate: symmetric sweeps or whole row blocks.  The launch lasts
-    // about max(work / waves, the longest row block, the sweeps' start + the longest
-    // sweep chain) tile-times, where
-    //   sweeps:  work T^2 / 2 + T,  chain chain_k T (each sweep starts ~2 tiles behind
-    //            the one before)
-    //   rows:    work row_k T^2,    chain row_k T   (every ordered pair, no chain)
-    // Whole row blocks are first in the queue, so when they hold more than the waves
-    // the sweeps start late (start = their work / waves).  The k largest aggregates
-    // run as row blocks, k minimising the prediction; no mix whose row blocks hold
-    // more than half the waves (their raised waves delay and slow the sweeps: per-rank
-    // shares of C4, N = 4: 20 of 24 aggregates as row blocks 70 ms per iteration, 7 of
-    // 25 58 ms).  At N = 1 (C4) the launch is work-bound and every aggregate sweeps;
-    // the shares of a multi-GPU run are chain-bound.
-    // row_k: a row-block tile (64 x 64 ordered pairs) against a sweep tile (64 x 64
-    // unordered), wave time at full load -- 0.6 measured on an N = 8 share of C4
-    // (all row blocks: 17.9 us per row tile per wave, against 29.8 us per sweep tile
-    // at N = 1; profiles/r04/sym_timeline_rows_n8.json)
-    double chain_k = 2.5;
-    const double row_k = 0.6;
-    if (const char* e = std::getenv("GE_FAML_SYM_CHAIN")) chain_k = std::atof(e);  // 0: all sweeps
-    std::vector<char> as_rows(big.size(), 0);
-    double best = 0.0;
-    if (chain_k > 0.0 && any_big) {
-      std::vector<size_t> by_T(big.size());
-      std::iota(by_T.begin(), by_T.end(), 0);
-      std::stable_sort(by_T.begin(), by_T.end(), [&](size_t x, size_t y) { return T[x] > T[y]; });
-      double work = 0.0, row_work = 0.0, row_units = 0.0, pbest = 1e300;
-      size_t best_k = 0;
-      for (size_t b = 0; b < big.size(); ++b) work += 0.5 * T[b] * (double)T[b] + T[b];
-      for (size_t k = 0; k <= by_T.size(); ++k) {  // the k largest as row blocks
-        const double start = row_units > waves ? row_work / waves : 0.0;
-        const double sweep_chain = k < by_T.size() ? start + chain_k * T[by_T[k]] : 0.0;
-        const double row_path = k > 0 ? row_k * T[by_T[0]] : 0.0;
-        const double pred = std::max(work / waves, std::max(sweep_chain, row_path));
-        const bool mixed_late = 2.0 * row_units > waves && k < by_T.size();
-        if (!mixed_late && pred < pbest * 0.999) {
-          pbest = pred;
-          best_k = k;
-        }
-        if (k < by_T.size()) {
-          const double t = T[by_T[k]];
-          work += row_k * t * t - (0.5 * t * t + t);
-          row_work += row_k * t * t;
-          row_units += t;
-        }
-      }
-      for (size_t k = 0; k < best_k; ++k) as_rows[by_T[k]] = 1;
-      best = pbest;
-    }
-    pl->rows_mode = pl->swept = 0;
-    for (size_t b = 0; b < big.size(); ++b) {
-      if (as_rows[b]) ++pl->rows_mode;
-      else ++pl->swept;
-    }
-    struct Unit { int a, A, pb, T, kind; double est; };
-    std::vector<Unit> us;
-    int pb = 0;
-    // Queue position of sweep A of an aggregate of T row tiles: 2A Tmax / T, i.e.
-    // every aggregate's sweeps spread over the whole queue, so all aggregates reach
-    // their last (chain-bound) sweeps together and the launch ends without a tail of
-    // the largest aggregate's chain (C4: tail after the queue drained 8.7 -> 3.5 ms,
-    // 148.1 -> 143.2 ms per launch; 2A alone, the sweep's earliest start, was the
-    // round-2 order).  Every sweep comes after the sweeps it waits on (sweep A - 1
-    // before A).
-    const double est_k = 2.0;
-    const int Tmax = big.empty() ? 1 : *std::max_element(T.begin(), T.end());
-    // Big aggregates a little ahead: positions also scaled by 1 - g T / Tmax (g = 0.3),
-    // so the largest chains finish before the queue's end and the small aggregates'
-    // short chains fill it (C4, one box, 3 rounds interleaved: 136.2-136.4 against
-    // 136.9-137.3 ms per step; g = 0.15 136.5-136.7, 0.5 and 0.7 slower;
-    // profiles/r04/ab_big_first.log).  Positions stay increasing in A for g < 1, so
-    // every unit still waits only on units before it.
-    const double big_first = 0.3;
-    auto scale_of = [&](int Tb) {
-      return ((double)Tmax / Tb) * (1.0 - big_first * Tb / Tmax);
-    };
-    // row blocks' issue priority: one level per quarter of the longest row block's
-    // column tiles (ge_sym.hpp rows_prio; one level per sixth or eighth: no different,
-    // profiles/r05/scale_sim_c4_prio_divisor.log)
-    int rows_q = 0;
-    const int prio_div = 4;
-    for (size_t b = 0; b < big.size(); ++b)
-      if (as_rows[b]) rows_q = std::max(rows_q, T[b]);
-    for (int a : split) rows_q = std::max(rows_q, (h_pt_ip[a + 1] - h_pt_ip[a] + 63) / 64);
-    rows_q = (rows_q + prio_div - 1) / prio_div;
-    for (size_t b = 0; b < big.size(); ++b) {
-      if (as_rows[b]) {
-        // row blocks have no dependencies and each spans its aggregate's whole width:
-        // first in the queue, longest first (measured on per-rank shares of C4: N = 4
-        // 69 ms per iteration against 80 ms when spread among the sweeps).  Round 5
-        // tried cutting the last-taken blocks into a head and a tail segment
-        // (McNaughton's wrap-around, so the queue's last round is short): bit-exact,
-        // no faster (N = 8 shares 26.6-28.0 against 27.0-27.3 ms per launch,
-        // profiles/r05/scale_sim_c4_tailsplit.log) -- the share is bound by the row
-        // blocks' instruction stream, not by the queue's last round.
-        for (int A = 0; A < T[b]; ++A) us.push_back({big[b], A, rows_q, T[b], kUnitRows, -1.0});
-        continue;
-      }
-      const double sc = scale_of(T[b]);
-      // (round 6 measured sweep issue priorities by the followers a sweep holds up:
-      // 115.8-116.0 against 115.3-115.4 ms per launch, profiles/r06/ab_sym_prio.log)
-      for (int A = 0; A < T[b]; ++A) us.push_back({big[b], A, pb, T[b], kUnitSweep, est_k * A * sc});
-      pb += T[b];
-    }
-    for (int a : split) {  // this rank's row tiles of the split aggregates: row blocks
-      int t0, t1;
-      tiles_of(a, rank, t0, t1);
-      const int Ta = (h_pt_ip[a + 1] - h_pt_ip[a] + 63) / 64;
-      for (int A = t0; A < t1; ++A) us.push_back({a, A, rows_q, Ta, kUnitRows, -1.0});
-    }
-    std::stable_sort(us.begin(), us.end(), [](const Unit& x, const Unit& y) {
-      return x.est != y.est ? x.est < y.est : x.T > y.T;
-    });
-    std::vector<int4> h_units;
-    for (const Unit& x : us) h_units.push_back(make_int4(x.a, x.A, x.pb, x.kind));
-    pl->nunits = (int)h_units.size();
-    pl->ntiles = pb;
-    pl->units.alloc(h_units.size());
-    pl->units.upload(h_units.data(), h_units.size(), st);
+  if (s.sym && !s.huge.empty()) {  // sweep units, hand-over buffers and progress counters
+    pl->units.alloc(s.units.size());
+    pl->units.upload(reinterpret_cast<const int4*>(s.units.data()), s.units.size(), st);
     if (const char* e = std::getenv("GE_SYM_STAMPS")) {  // diagnostics: timeline of each launch
       pl->stamp_path = e;
-      pl->h_units = h_units;
-      pl->stamps.alloc(h_units.size() * kStampWords);
+      pl->h_units = s.units;
+      pl->stamps.alloc(s.units.size() * kStampWords);
     }
-    pl->prog.alloc(std::max(pb, 1));
-    if (pb > 0) pl->hand.alloc((size_t)pl->n * dim);
+    pl->prog.alloc(std::max(s.ntiles, 1));
+    if (s.ntiles > 0) pl->hand.alloc((size_t)n * dim);
     pl->sym_err.alloc(1);
     GE_HIP(hipMemsetAsync(pl->sym_err.p, 0, sizeof(int), st));
-    int khz = 0;
+    int dev = 0, khz = 0;
+    GE_HIP(hipGetDevice(&dev));
     GE_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
     // one hand-over normally waits at most a few tile-times (tens of microseconds)
     pl->sym_limit = (long long)std::max(khz, 1000) * 5000;  // ~5 s
   }
-  pl->R = R;
-  pl->code = big_code(R, U);
-  for (int a : big) {
-    const double sa = h_pt_ip[a + 1] - h_pt_ip[a];
-    pl->streamed_pairs += sa * (sa - 1);
-  }
-  for (int a : split) {  // this rank's rows against all members
-    int t0, t1;
-    tiles_of(a, rank, t0, t1);
-    const double sa = h_pt_ip[a + 1] - h_pt_ip[a];
-    pl->streamed_pairs += (std::min(sa, 64.0 * t1) - std::min(sa, 64.0 * t0)) * (sa - 1);
-  }
   // 4 waves per SIMD: more items per wave for the queue to balance (C3 level
   // 0: 961 ms per call against 1091 ms at the full 8 waves per SIMD)
-  const int occ = rep_occupancy(dim, pl->code);
-  const int blocks_cu = std::min(4, occ);
-  pl->rep_blocks = cus * blocks_cu;
+  pl->rep_blocks = cus * std::min(4, rep_occupancy(dim, pl->code));
   if (pl->fast) {  // four waves per SIMD, the occupancy faml_fast_repulse is built for
     int focc = 1;
     dispatch_dim_narrow(dim, [&](auto Dc) {
@@ -1273,49 +1024,32 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
           &focc, (const void*)faml_fast_repulse<D, kFastR>, kHT, 0));
     });
     pl->fast_blocks = cus * std::min(4, std::max(focc, 1));
-    pl->fitems.alloc(fitems.size());
-    pl->fitems.upload(fitems.data(), fitems.size(), st);
+    pl->fitems.alloc(s.fitems.size());
+    pl->fitems.upload(reinterpret_cast<const int4*>(s.fitems.data()), s.fitems.size(), st);
   }
-  std::vector<int> begs;
-  begs.insert(begs.end(), beg_s.begin(), beg_s.end());
-  pl->off_m = begs.size();
-  begs.insert(begs.end(), beg_m.begin(), beg_m.end());
-  pl->off_l = begs.size();
-  begs.insert(begs.end(), beg_l.begin(), beg_l.end());
-  pl->ns = (int)beg_s.size() - 1;
-  pl->nm = (int)beg_m.size() - 1;
-  pl->nl = (int)beg_l.size() - 1;
-  pl->nrows = (int)rows.size();
-  pl->nirows = (int)irows.size();
-  pl->nitems = (int)items.size();
-  std::vector<int> huge = big;  // centred and scaled at the end: the split ones on every rank
-  huge.insert(huge.end(), split.begin(), split.end());
-  pl->nhuge = (int)huge.size();
-
-  const int n = pl->n;
   pl->pos.alloc(std::max(n, 1));
-  pl->order.alloc(std::max<size_t>(order.size(), 1));
-  pl->beg.alloc(std::max<size_t>(begs.size(), 1));
-  pl->rows.alloc(std::max<size_t>(rows.size(), 1));
-  pl->items.alloc(std::max<size_t>(items.size(), 1));
+  pl->order.alloc(std::max<size_t>(s.order.size(), 1));
+  pl->beg.alloc(std::max<size_t>(s.beg.size(), 1));
+  pl->rows.alloc(std::max<size_t>(s.rows.size(), 1));
+  pl->items.alloc(std::max<size_t>(s.items.size(), 1));
   pl->queue.alloc(std::max(pl->iterations, 1));
-  pl->huge.alloc(std::max<size_t>(huge.size(), 1));
-  pl->irows.alloc(std::max<size_t>(irows.size(), 1));
-  pl->irows.upload(irows.data(), irows.size(), st);
-  pl->order.upload(order.data(), order.size(), st);
-  pl->beg.upload(begs.data(), begs.size(), st);
-  pl->rows.upload(rows.data(), rows.size(), st);
-  pl->items.upload(items.data(), items.size(), st);
-  pl->huge.upload(huge.data(), huge.size(), st);
+  pl->huge.alloc(std::max<size_t>(s.huge.size(), 1));
+  pl->irows.alloc(std::max<size_t>(s.irows.size(), 1));
+  pl->irows.upload(s.irows.data(), s.irows.size(), st);
+  pl->order.upload(s.order.data(), s.order.size(), st);
+  pl->beg.upload(s.beg.data(), s.beg.size(), st);
+  pl->rows.upload(s.rows.data(), s.rows.size(), st);
+  pl->items.upload(reinterpret_cast<const int2*>(s.items.data()), s.items.size(), st);
+  pl->huge.upload(s.huge.data(), s.huge.size(), st);
   if (!split.empty() && nranks > 1) {  // the per-iteration exchange of the split rows
-    pl->h_xcounts = xcounts;
+    pl->h_xcounts = s.xcounts;
     pl->h_xfirst.assign(nranks + 1, 0);
-    for (int r = 0; r < nranks; ++r) pl->h_xfirst[r + 1] = pl->h_xfirst[r] + xcounts[r];
-    pl->xwidth = std::max(1, *std::max_element(xcounts.begin(), xcounts.end()));
-    pl->xrows.alloc(std::max<size_t>(xr.size(), 1));
-    pl->xrows.upload(xr.data(), xr.size(), st);
+    for (int r = 0; r < nranks; ++r) pl->h_xfirst[r + 1] = pl->h_xfirst[r] + s.xcounts[r];
+    pl->xwidth = std::max(1, *std::max_element(s.xcounts.begin(), s.xcounts.end()));
+    pl->xrows.alloc(std::max<size_t>(s.xr.size(), 1));
+    pl->xrows.upload(s.xr.data(), s.xr.size(), st);
     pl->xcounts.alloc(nranks);
-    pl->xcounts.upload(xcounts.data(), nranks, st);
+    pl->xcounts.upload(s.xcounts.data(), nranks, st);
     pl->xfirst.alloc(nranks + 1);
     pl->xfirst.upload(pl->h_xfirst.data(), nranks + 1, st);
     pl->xbuf.alloc((size_t)pl->xwidth * dim * nranks);
@@ -1409,17 +1143,7 @@ static void faml_plan_repulse(ge_faml_plan* pl, const double* x, double* frep) {
 static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, const double* init,
                           double* X) {
   hipStream_t st = pl->ctx->stream;
-  hipEvent_t* ev = nullptr;
-  if (pl->profiling) {
-    if (pl->next_ev + 4 > pl->ev.size())
-      for (int k = 0; k < 64; ++k) {
-        hipEvent_t e;
-        GE_HIP(hipEventCreate(&e));
-        pl->ev.push_back(e);
-      }
-    ev = &pl->ev[pl->next_ev];
-    pl->next_ev += 4;
-  }
+  hipEvent_t* ev = pl->profiling ? pl->ev.take(4) : nullptr;
   const int iters = pl->iterations;
   const FaConst& c = pl->c;
   dispatch_dim(pl->dim, [&](auto Dc) {
@@ -1455,34 +1179,14 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
       double* cur = pl->Xa.p;
       double* nxt = pl->Xb.p;
       for (int it = 0; it < iters; ++it) {
-        hipEvent_t* re = nullptr;
-        if (pl->profiling) {
-          if (pl->next_rev + 2 > pl->rev.size())
-            for (int k = 0; k < 256; ++k) {
-              hipEvent_t e;
-              GE_HIP(hipEventCreate(&e));
-              pl->rev.push_back(e);
-            }
-          re = &pl->rev[pl->next_rev];
-          pl->next_rev += 2;
-          GE_HIP(hipEventRecord(re[0], ss));
-        }
+        hipEvent_t* re = pl->profiling ? pl->rev.take(2) : nullptr;
+        if (re) GE_HIP(hipEventRecord(re[0], ss));
         const FamlRows<D> fr{pl->pt_ip, pl->pt_ix, pl->ecode.p, pl->ip, pl->vA, pl->dx,
                              cA, cur, pl->DP.p, pl->Fscr.p, nxt, pl->Fprev.p, c};
         faml_launch_repulse<D>(pl, ss, pl->queue.p + it, cur, pl->Fscr.p);
         if (re) GE_HIP(hipEventRecord(re[1], ss));
-        hipEvent_t* ae = nullptr;
-        if (pl->profiling) {
-          if (pl->next_aev + 2 > pl->aev.size())
-            for (int k = 0; k < 256; ++k) {
-              hipEvent_t e;
-              GE_HIP(hipEventCreate(&e));
-              pl->aev.push_back(e);
-            }
-          ae = &pl->aev[pl->next_aev];
-          pl->next_aev += 2;
-          GE_HIP(hipEventRecord(ae[0], ss));
-        }
+        hipEvent_t* ae = pl->profiling ? pl->aev.take(2) : nullptr;
+        if (ae) GE_HIP(hipEventRecord(ae[0], ss));
         if (pl->nrows > 0) launch_rows<D>(pl->ecls, fr, ss, pl->rstreams);
         if (ae) GE_HIP(hipEventRecord(ae[1], ss));
         if (pl->xwidth > 0)  // every rank's rows of the split aggregates, for the next step
@@ -1512,7 +1216,7 @@ static void faml_plan_run(ge_faml_plan* pl, const double* cA, const double* rA, 
     if (FILE* f = std::fopen(pl->stamp_path.c_str(), "wb")) {
       const int hdr[4] = {pl->nunits, kStampWords, pl->sym_blocks, kSymT};
       std::fwrite(hdr, sizeof(int), 4, f);
-      std::fwrite(pl->h_units.data(), sizeof(int4), pl->h_units.size(), f);
+      std::fwrite(pl->h_units.data(), sizeof(SchedInt4), pl->h_units.size(), f);
       std::fwrite(h.data(), sizeof(long long), h.size(), f);
       std::fclose(f);
     }
@@ -1539,15 +1243,7 @@ void sym_repulse_launch(int dim, int blocks, hipStream_t s, int nunits, const in
 // tiles: one convoy of sweeps, each behind the one before).  Two of the four that
 // fit: C2 1539.8 ms per iteration against 1631.9 at three and 1806.8 at four
 // (profiles/r04/c2_sym_blocks.log) -- fewer sweeps in flight wait less on each other.
-int sym_blocks_per_cu(int dim) {
-  int occ = 1;
-  dispatch_dim_narrow(dim, [&](auto Dc) {
-    constexpr int D = decltype(Dc)::value;
-    GE_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &occ, (const void*)faml_sym_repulse<D, false>, kSymT, 0));
-  });
-  return std::min(std::max(occ, 1), 2);
-}
+int sym_blocks_per_cu(int dim) { return std::min(std::max(sym_occupancy(dim), 1), 2); }
 
 static void faml_plan_free(ge_faml_plan* pl) {
   if (!pl) return;
@@ -1559,10 +1255,28 @@ static void faml_plan_free(ge_faml_plan* pl) {
     if (pl->join[k]) (void)hipEventDestroy(pl->join[k]);
   }
   if (pl->fork) (void)hipEventDestroy(pl->fork);
-  for (hipEvent_t e : pl->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : pl->rev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : pl->aev) (void)hipEventDestroy(e);
   delete pl;
+}
+
+// The caller's graph, P_T and parameters of a new plan.
+static void fill_plan(ge_faml_plan* pl, ge_ctx* ctx, ge_comm* comm, int n, const int* d_ip,
+                      const int* d_ix, const double* d_dx, int m, const int* d_pt_ip,
+                      const int* d_pt_ix, const int* d_vA, int dim, int iterations,
+                      const ge_fa_params& p) {
+  pl->ctx = ctx;
+  pl->comm = comm;
+  pl->n = n;
+  pl->m = m;
+  pl->dim = dim;
+  pl->iterations = iterations;
+  pl->ip = d_ip;
+  pl->ix = d_ix;
+  pl->dx = d_dx;
+  pl->pt_ip = d_pt_ip;
+  pl->pt_ix = d_pt_ix;
+  pl->vA = d_vA;
+  pl->c = make_fa_const(p);
+  pl->mode = far_as_fast(p).mode;
 }
 
 void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const double* d_dx,
@@ -1573,19 +1287,7 @@ void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const
   GE_REQUIRE(h_pt_ip[m] == n, "P_T must have one entry per fine vertex");
   auto* pl = new ge_faml_plan();
   try {
-    pl->ctx = ctx;
-    pl->n = n;
-    pl->m = m;
-    pl->dim = dim;
-    pl->iterations = iterations;
-    pl->ip = d_ip;
-    pl->ix = d_ix;
-    pl->dx = d_dx;
-    pl->pt_ip = d_pt_ip;
-    pl->pt_ix = d_pt_ix;
-    pl->vA = d_vA;
-    pl->c = make_fa_const(p);
-    pl->mode = far_as_fast(p).mode;
+    fill_plan(pl, ctx, nullptr, n, d_ip, d_ix, d_dx, m, d_pt_ip, d_pt_ix, d_vA, dim, iterations, p);
     std::vector<int> all(m);
     std::iota(all.begin(), all.end(), 0);
     faml_plan_build(pl, h_pt_ip, all);
@@ -1613,20 +1315,8 @@ static int faml_plan_create_impl(ge_ctx* ctx, int n, const int* d_ip, const int*
     ge::DeviceGuard g(ctx);
     auto* pl = new ge_faml_plan();
     try {
-      pl->ctx = ctx;
-      pl->comm = comm;
-      pl->n = n;
-      pl->m = m;
-      pl->dim = dim;
-      pl->iterations = iterations;
-      pl->ip = d_ip;
-      pl->ix = d_ix;
-      pl->dx = d_dx;
-      pl->pt_ip = d_pt_ip;
-      pl->pt_ix = d_pt_ix;
-      pl->vA = d_vA;
-      pl->c = ge::make_fa_const(*p);
-      pl->mode = ge::far_as_fast(*p).mode;
+      ge::fill_plan(pl, ctx, comm, n, d_ip, d_ix, d_dx, m, d_pt_ip, d_pt_ix, d_vA, dim,
+                    iterations, *p);
       ge::faml_plan_build(pl, h_pt_ip, aggs, split);
     } catch (...) {
       ge::faml_plan_free(pl);
@@ -1642,6 +1332,13 @@ static void faml_plan_check(ge_ctx* ctx, int n, int m, const int* h_pt_ip, int d
   GE_REQUIRE(dim >= 1 && dim <= ge::kMaxDim, "dimension must be 1..16");
   GE_REQUIRE(n > 0 && m > 0 && h_pt_ip[0] == 0 && h_pt_ip[m] == n,
              "P_T must have one entry per fine vertex");
+}
+
+// ids[0..cnt): strictly increasing aggregate ids below m, copied to `out`.
+static void check_ids(const int* ids, int cnt, int m, const char* msg, std::vector<int>& out) {
+  for (int q = 0; q < cnt; ++q)
+    GE_REQUIRE(ids[q] >= 0 && ids[q] < m && (q == 0 || ids[q] > ids[q - 1]), msg);
+  out.assign(ids, ids + cnt);
 }
 
 int ge_faml_plan_create(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const double* d_dx,
@@ -1669,10 +1366,7 @@ int ge_faml_plan_create_subset(ge_ctx* ctx, int n, const int* d_ip, const int* d
   const int rc = ge::guarded([&] {
     faml_plan_check(ctx, n, m, h_pt_ip, dim, p, out);
     GE_REQUIRE(n_aggs >= 0 && (h_aggs || n_aggs == 0), "bad aggregate list");
-    for (int q = 0; q < n_aggs; ++q)
-      GE_REQUIRE(h_aggs[q] >= 0 && h_aggs[q] < m && (q == 0 || h_aggs[q] > h_aggs[q - 1]),
-                 "aggregate ids must be strictly increasing and < m");
-    aggs.assign(h_aggs, h_aggs + n_aggs);
+    check_ids(h_aggs, n_aggs, m, "aggregate ids must be strictly increasing and < m", aggs);
   });
   if (rc != GE_OK) return rc;
   return faml_plan_create_impl(ctx, n, d_ip, d_ix, d_dx, m, h_pt_ip, d_pt_ip, d_pt_ix, d_vA, dim,
@@ -1690,19 +1384,12 @@ int ge_faml_plan_create_shard(ge_ctx* ctx, ge_comm* comm, int n, const int* d_ip
     GE_REQUIRE(comm && comm->ctx == ctx, "the communicator must belong to the plan's context");
     GE_REQUIRE(n_aggs >= 0 && (h_aggs || n_aggs == 0) && n_split >= 0 && (h_split || n_split == 0),
                "bad aggregate lists");
+    check_ids(h_aggs, n_aggs, m, "aggregate ids must be strictly increasing and < m", aggs);
+    check_ids(h_split, n_split, m, "split aggregate ids must be strictly increasing and < m",
+              split);
     std::vector<char> seen(m, 0);
-    for (int q = 0; q < n_aggs; ++q) {
-      GE_REQUIRE(h_aggs[q] >= 0 && h_aggs[q] < m && (q == 0 || h_aggs[q] > h_aggs[q - 1]),
-                 "aggregate ids must be strictly increasing and < m");
-      seen[h_aggs[q]] = 1;
-    }
-    for (int q = 0; q < n_split; ++q) {
-      GE_REQUIRE(h_split[q] >= 0 && h_split[q] < m && (q == 0 || h_split[q] > h_split[q - 1]),
-                 "split aggregate ids must be strictly increasing and < m");
-      GE_REQUIRE(!seen[h_split[q]], "an aggregate is both whole and split");
-    }
-    aggs.assign(h_aggs, h_aggs + n_aggs);
-    split.assign(h_split, h_split + n_split);
+    for (int a : aggs) seen[a] = 1;
+    for (int a : split) GE_REQUIRE(!seen[a], "an aggregate is both whole and split");
   });
   if (rc != GE_OK) return rc;
   return faml_plan_create_impl(ctx, n, d_ip, d_ix, d_dx, m, h_pt_ip, d_pt_ip, d_pt_ix, d_vA, dim,
@@ -1738,9 +1425,9 @@ int ge_faml_plan_set_profiling(ge_faml_plan* pl, int enable) {
   return ge::guarded([&] {
     GE_REQUIRE(pl, "null plan");
     pl->profiling = enable != 0;
-    pl->next_ev = 0;
-    pl->next_rev = 0;
-    pl->next_aev = 0;
+    pl->ev.reset();
+    pl->rev.reset();
+    pl->aev.reset();
   });
 }
 
@@ -1750,19 +1437,8 @@ int ge_faml_plan_kernel_ms(ge_faml_plan* pl, double* resident_ms, double* stream
     GE_REQUIRE(pl && resident_ms && streamed_ms && runs, "null argument");
     ge::DeviceGuard g(pl->ctx);
     GE_HIP(hipStreamSynchronize(pl->ctx->stream));
-    double a = 0, b = 0;
-    int cnt = 0;
-    for (size_t k = 0; k + 4 <= pl->next_ev; k += 4) {
-      float t1 = 0.f, t2 = 0.f;
-      GE_HIP(hipEventElapsedTime(&t1, pl->ev[k], pl->ev[k + 1]));
-      GE_HIP(hipEventElapsedTime(&t2, pl->ev[k + 2], pl->ev[k + 3]));
-      a += t1;
-      b += t2;
-      ++cnt;
-    }
-    *resident_ms = cnt ? a / cnt : 0.0;
-    *streamed_ms = cnt ? b / cnt : 0.0;
-    *runs = cnt;
+    *resident_ms = pl->ev.mean_ms(4, 0, 1, runs);
+    *streamed_ms = pl->ev.mean_ms(4, 2, 3);
   });
 }
 
@@ -1772,16 +1448,7 @@ int ge_faml_plan_repulse_ms(ge_faml_plan* pl, double* ms, int* launches, double*
     *pairs = pl->streamed_pairs;
     ge::DeviceGuard g(pl->ctx);
     GE_HIP(hipStreamSynchronize(pl->ctx->stream));
-    double t = 0;
-    int cnt = 0;
-    for (size_t k = 0; k + 2 <= pl->next_rev; k += 2) {
-      float x = 0.f;
-      GE_HIP(hipEventElapsedTime(&x, pl->rev[k], pl->rev[k + 1]));
-      t += x;
-      ++cnt;
-    }
-    *ms = cnt ? t / cnt : 0.0;
-    *launches = cnt;
+    *ms = pl->rev.mean_ms(2, 0, 1, launches);
   });
 }
 
@@ -1793,16 +1460,7 @@ int ge_faml_plan_rows_ms(ge_faml_plan* pl, double* ms, int* passes, long long* r
     *entries = pl->streamed_entries;
     ge::DeviceGuard g(pl->ctx);
     GE_HIP(hipStreamSynchronize(pl->ctx->stream));
-    double t = 0;
-    int cnt = 0;
-    for (size_t k = 0; k + 2 <= pl->next_aev; k += 2) {
-      float x = 0.f;
-      GE_HIP(hipEventElapsedTime(&x, pl->aev[k], pl->aev[k + 1]));
-      t += x;
-      ++cnt;
-    }
-    *ms = cnt ? t / cnt : 0.0;
-    *passes = cnt;
+    *ms = pl->aev.mean_ms(2, 0, 1, passes);
   });
 }
 
@@ -1834,6 +1492,74 @@ int ge_faml_plan_classes(ge_faml_plan* pl, int* res_cap, int* aggregates, int* b
 
 int ge_faml_plan_destroy(ge_faml_plan* pl) {
   return ge::guarded([&] { ge::faml_plan_free(pl); });
+}
+
+struct ge_faml_sched {
+  ge::FamlSched s;
+  std::vector<int> scalars;
+};
+
+int ge_faml_sched_create(int m, const int* h_pt_ip, const int* h_aggs, int n_aggs,
+                         const int* h_split, int n_split, int rank, int nranks, int dim, int mode,
+                         int cus, int sym_occ, ge_faml_sched** out) {
+  return ge::guarded([&] {
+    GE_REQUIRE(out && h_pt_ip && m >= 0, "null argument");
+    GE_REQUIRE(dim >= 1 && dim <= ge::kMaxDim, "dimension must be 1..16");
+    GE_REQUIRE(n_aggs >= 0 && (h_aggs || n_aggs == 0) && n_split >= 0 && (h_split || n_split == 0),
+               "bad aggregate lists");
+    GE_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks && cus >= 1, "bad rank / size");
+    std::vector<int> aggs, split;
+    check_ids(h_aggs, n_aggs, m, "aggregate ids must be strictly increasing and < m", aggs);
+    check_ids(h_split, n_split, m, "split aggregate ids must be strictly increasing and < m",
+              split);
+    auto* h = new ge_faml_sched();
+    std::unique_ptr<ge_faml_sched> hold(h);
+    h->s = ge::faml_schedule(ge::faml_sched_in(h_pt_ip, aggs, split, rank, nranks, dim,
+                                               mode == GE_MODE_FARFIELD ? GE_MODE_FAST : mode, cus,
+                                               sym_occ));
+    const ge::FamlSched& s = h->s;
+    h->scalars = {s.res_cap, s.census[0], s.census[1], s.census[2], s.census[3],
+                  (int)s.off_m, (int)s.off_l, s.ns, s.nm, s.nl,
+                  s.R, s.U, s.code, (int)s.fast, (int)s.sym,
+                  (int)s.wide, s.ntiles, s.swept, s.rows_mode, s.sym_blocks};
+    *out = hold.release();
+  });
+}
+
+int ge_faml_sched_table(const ge_faml_sched* h, int k, const int** data, long long* len) {
+  return ge::guarded([&] {
+    GE_REQUIRE(h && data && len, "null argument");
+    const ge::FamlSched& s = h->s;
+    auto put = [&](const void* p, size_t ints) {
+      *data = (const int*)p;
+      *len = (long long)ints;
+    };
+    switch (k) {
+      case GE_FAML_SCHED_ORDER: put(s.order.data(), s.order.size()); break;
+      case GE_FAML_SCHED_BEG: put(s.beg.data(), s.beg.size()); break;
+      case GE_FAML_SCHED_ROWS: put(s.rows.data(), s.rows.size()); break;
+      case GE_FAML_SCHED_IROWS: put(s.irows.data(), s.irows.size()); break;
+      case GE_FAML_SCHED_HUGE: put(s.huge.data(), s.huge.size()); break;
+      case GE_FAML_SCHED_XROWS: put(s.xr.data(), s.xr.size()); break;
+      case GE_FAML_SCHED_XCOUNTS: put(s.xcounts.data(), s.xcounts.size()); break;
+      case GE_FAML_SCHED_ITEMS: put(s.items.data(), 2 * s.items.size()); break;
+      case GE_FAML_SCHED_FITEMS: put(s.fitems.data(), 4 * s.fitems.size()); break;
+      case GE_FAML_SCHED_UNITS: put(s.units.data(), 4 * s.units.size()); break;
+      case GE_FAML_SCHED_SCALARS: put(h->scalars.data(), h->scalars.size()); break;
+      default: throw ge::Error(GE_ERR_ARG, "unknown schedule table");
+    }
+  });
+}
+
+int ge_faml_sched_pairs(const ge_faml_sched* h, double* streamed_pairs) {
+  return ge::guarded([&] {
+    GE_REQUIRE(h && streamed_pairs, "null argument");
+    *streamed_pairs = h->s.streamed_pairs;
+  });
+}
+
+int ge_faml_sched_destroy(ge_faml_sched* h) {
+  return ge::guarded([&] { delete h; });
 }
 
 }  // extern "C"

@@ -99,6 +99,52 @@ struct DevBuf {
   }
 };
 
+// Profiling events: taken in groups (one per timed step, launch or pass), created a
+// chunk at a time, reused from the start after reset().
+struct EventPool {
+  std::vector<hipEvent_t> ev;
+  size_t next = 0, chunk;
+  explicit EventPool(size_t chunk_) : chunk(chunk_) {}
+  EventPool(const EventPool&) = delete;
+  EventPool& operator=(const EventPool&) = delete;
+  ~EventPool() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  // k consecutive events, valid until the next take()
+  hipEvent_t* take(size_t k) {
+    if (next + k > ev.size())
+      for (size_t q = 0; q < chunk; ++q) {
+        hipEvent_t e;
+        GE_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+      }
+    next += k;
+    return &ev[next - k];
+  }
+  void reset() { next = 0; }
+  // Mean ms from event a to event b of the groups of `stride` taken since reset()
+  // (all recorded and complete); groups: how many.
+  double mean_ms(size_t stride, size_t a, size_t b, int* groups = nullptr) const {
+    double t = 0.0;
+    int cnt = 0;
+    for (size_t k = 0; k + stride <= next; k += stride) {
+      float x = 0.f;
+      GE_HIP(hipEventElapsedTime(&x, ev[k + a], ev[k + b]));
+      t += x;
+      ++cnt;
+    }
+    if (groups) *groups = cnt;
+    return cnt ? t / cnt : 0.0;
+  }
+};
+
+inline int device_cus() {
+  int dev = 0, cus = 0;
+  GE_HIP(hipGetDevice(&dev));
+  GE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return cus > 0 ? cus : 256;
+}
+
 // Device copy of a host CSR.
 struct DevCsr {
   DevBuf<int> ip, ix;

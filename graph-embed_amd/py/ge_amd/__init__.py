@@ -149,6 +149,14 @@ _SIGS = {
                                             ctypes.POINTER(ctypes.c_longlong),
                                             ctypes.POINTER(ctypes.c_longlong)]),
     "ge_faml_plan_destroy": (ctypes.c_int, [_vp]),
+    "ge_faml_sched_create": (ctypes.c_int, [ctypes.c_int, _i32p, _i32p, ctypes.c_int, _i32p,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(_vp)]),
+    "ge_faml_sched_table": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_ip),
+                                           ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_faml_sched_pairs": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "ge_faml_sched_destroy": (ctypes.c_int, [_vp]),
     "ge_selftest_math": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_ulonglong,
                                         ctypes.POINTER(ctypes.c_longlong)]),
     "ge_math_cases": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, _f64p,
@@ -583,6 +591,42 @@ def row_shard(n, nranks, rank):
     a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     _check(lib().ge_row_shard(n, nranks, rank, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
     return a.value, b.value, c.value
+
+
+FAML_SCHED_TABLES = ("order", "beg", "rows", "irows", "huge", "xrows", "xcounts", "items",
+                     "fitems", "units")  # GE_FAML_SCHED_*; the scalars follow
+FAML_SCHED_SCALARS = ("res_cap", "small", "mid", "large", "streamed", "off_mid", "off_large",
+                      "blocks_small", "blocks_mid", "blocks_large", "R", "U", "code", "fast",
+                      "sym", "wide", "ntiles", "sweeps", "row_blocks", "sym_blocks")
+
+
+def faml_schedule(pt_indptr, dim, cus, sym_occ, aggs=None, split=None, rank=0, nranks=1,
+                  mode=MODE_STRICT):
+    """The schedule a FamlPlan over these aggregates would settle on, without a device
+    (ge_faml_sched_*): {table name: int32 array} for FAML_SCHED_TABLES, the scalars of
+    FAML_SCHED_SCALARS and streamed_pairs.  aggs: default all; the GE_FAML_* knobs
+    are read from the environment as the plan reads them."""
+    pip = np.ascontiguousarray(pt_indptr, dtype=np.int32)
+    m = len(pip) - 1
+    ids = np.ascontiguousarray(np.arange(m) if aggs is None else aggs, dtype=np.int32)
+    sp = np.ascontiguousarray(np.zeros(0) if split is None else split, dtype=np.int32)
+    h = _vp()
+    _check(lib().ge_faml_sched_create(m, pip, ids, len(ids), sp, len(sp), rank, nranks, dim,
+                                      mode, cus, sym_occ, ctypes.byref(h)))
+    try:
+        out = {}
+        for k, name in enumerate(FAML_SCHED_TABLES + ("scalars",)):
+            p, n = _ip(), ctypes.c_longlong()
+            _check(lib().ge_faml_sched_table(h, k, ctypes.byref(p), ctypes.byref(n)))
+            out[name] = (np.ctypeslib.as_array(p, (n.value,)).astype(np.int32) if n.value
+                         else np.zeros(0, dtype=np.int32))
+        out.update(zip(FAML_SCHED_SCALARS, (int(v) for v in out.pop("scalars"))))
+        d = ctypes.c_double()
+        _check(lib().ge_faml_sched_pairs(h, ctypes.byref(d)))
+        out["streamed_pairs"] = d.value
+    finally:
+        lib().ge_faml_sched_destroy(h)
+    return out
 
 
 class FamlPlan:

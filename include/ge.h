@@ -330,6 +330,37 @@ int ge_faml_plan_schedule(ge_faml_plan* plan, int* sweeps, int* banded, int* row
 int ge_faml_plan_classes(ge_faml_plan* plan, int* res_cap, int* aggregates, int* blocks,
                          int* rows);
 int ge_faml_plan_destroy(ge_faml_plan* plan);
+/* The schedule a plan would settle on, computed on the host alone (no device is
+ * touched): what ge_faml_plan_create* builds from P_T's indptr, the aggregate lists
+ * (h_split: the aggregates split over nranks ranks, as ge_faml_plan_create_shard),
+ * the dimension, ge_fa_params.mode and the GE_FAML_* environment, given the device's
+ * CU count and the blocks per CU of the symmetric sweep kernel (sym_occ).  Tables are
+ * int arrays owned by the handle: the resident packs' aggregates and their block
+ * offsets (small, mid, large), this rank's streamed rows, the rows it initialises,
+ * the aggregates centred at the end, the split rows by rank and their counts, the
+ * STRICT items (2 ints each), the FAST items and the sweep units (4 ints each), and
+ * the scalars {res_cap, aggregates[4], mid and large offsets into the block table,
+ * blocks[3], R, U, variant code, fast, sym, wide, progress tiles, sweeps, row blocks,
+ * sym blocks}.  Diagnostics and tests; the results do not depend on the schedule. */
+typedef struct ge_faml_sched ge_faml_sched;
+#define GE_FAML_SCHED_ORDER 0
+#define GE_FAML_SCHED_BEG 1
+#define GE_FAML_SCHED_ROWS 2
+#define GE_FAML_SCHED_IROWS 3
+#define GE_FAML_SCHED_HUGE 4
+#define GE_FAML_SCHED_XROWS 5
+#define GE_FAML_SCHED_XCOUNTS 6
+#define GE_FAML_SCHED_ITEMS 7
+#define GE_FAML_SCHED_FITEMS 8
+#define GE_FAML_SCHED_UNITS 9
+#define GE_FAML_SCHED_SCALARS 10
+int ge_faml_sched_create(int m, const int* h_pt_indptr, const int* h_aggs, int n_aggs,
+                         const int* h_split, int n_split, int rank, int nranks, int dim,
+                         int mode, int cus, int sym_occ, ge_faml_sched** out);
+int ge_faml_sched_table(const ge_faml_sched* sched, int k, const int** data, long long* len);
+/* Ordered pairs one repulsion launch of the streamed rows evaluates. */
+int ge_faml_sched_pairs(const ge_faml_sched* sched, double* streamed_pairs);
+int ge_faml_sched_destroy(ge_faml_sched* sched);
 
 /* ---- coarsening hierarchy ----
  * Replaces std::vector<SparseMatrix> partition::partition(A, coarseningFactor,

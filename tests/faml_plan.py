@@ -2,9 +2,9 @@
 which kernels ran it (test infrastructure for the GPU tests).
 
 run_plan returns the coordinates with the plan's census (FamlPlan.classes()) and
-schedule (FamlPlan.schedule()); expected_classes restates faml_plan_build's
-bucketing (graph-embed_amd/csrc/ge_faml.hip) from the sizes, the dimension and
-the device's CU count, so a test asserts the path it means to cover instead of
+schedule (FamlPlan.schedule()); expected_classes restates the scheduler's
+bucketing (classes_and_packs, graph-embed_amd/csrc/ge_faml_sched.hpp) from the
+sizes, the dimension and the device's CU count, so a test asserts the path it means to cover instead of
 claiming it in a comment.
 """
 import math
