@@ -74,14 +74,70 @@ __device__ __forceinline__ long long rt_now() { return (long long)__builtin_amdg
 // tiles ran as fast but its 6 KB more LDS per block locked the resident classes'
 // kernels out of the CUs during the repulsion launch: attraction passes 4.48 against
 // 3.54 ms, profiles/r06/ab_colring.log.)
-// Records {x[D], deg+1} are component-major in the ring `rec` (D + 1 components,
-// kRecSlots slots each): column q at slot q & 127, and slots 0..63 mirrored at
-// 128..191, so that within a column tile every lane reads slot ((64 tt - l) & 127) + j
-// at step 64 tt + j without wrapping: the per-step addresses are immediate offsets.
+// Records {x[D], deg+1} sit in the ring `rec` as 16-byte halves (round 17): components
+// 2h and 2h + 1 of a column share one 16-byte slot of region h, so a record is read with
+// one ds_read_b128 per half (half the LDS-array cycles of the ds_read2_b64 pairs of a
+// component-major ring).  D = 3: {x0, x1} and {x2, deg+1}; D = 1: {x0, deg+1}; at D = 2
+// the odd component out, deg+1, keeps a plain 8-byte region behind the half, so the ring
+// takes (D + 1) * kRecSlots doubles at every D, as before.  D = 4 keeps all five
+// components in 8-byte regions (SymRec<4>::halves = 0): with two halves the four-register
+// groups of the b128 reads took <4, false> from 119 to 121 VGPRs, past the 120 of
+// faml_sym_repulse.  Column q is at slot q & 127 of every region, and slots 0..63 are
+// mirrored at 128..191, so that within a column tile every lane reads slot
+// ((64 tt - l) & 127) + j at step 64 tt + j without wrapping: the per-step addresses are
+// immediate offsets from one base (a second one for the 8-byte regions, whose slots are
+// 8 bytes apart).  rec_read / rec_write are the only code that knows the layout.
 constexpr int kColSlots = 128;  // column ring: tile tt - 1 at 0..63, tile tt at 64..127
 constexpr int kSymRing = 128;   // record ring period (column q at q & 127)
 constexpr int kRecSlots = 192;  // record ring: 128 slots + the first 64 mirrored
 constexpr int kColBase = 64;    // the current tile's first slot
+
+typedef double rec_half __attribute__((ext_vector_type(2)));  // 16 bytes, 16-byte aligned
+
+#ifndef GE_SYM_HALVES4  // tuning switch (scripts/build_variant.sh): halves at D = 4
+#define GE_SYM_HALVES4 0
+#endif
+
+template <int D>
+struct SymRec {
+  static constexpr int halves = D == 4 ? GE_SYM_HALVES4 : (D + 1) / 2;  // 16-byte regions
+  static constexpr int half_len = 2 * kRecSlots;  // doubles per 16-byte region
+  static constexpr int tail = halves * half_len;  // first double of the 8-byte regions
+};
+
+// The record of ring slot `slot` (0..191): xq[0..D-1] = x, xq[D] = deg+1.
+template <int D>
+__device__ __forceinline__ void rec_read(const double* rec, int slot, double (&xq)[D + 1]) {
+  using R = SymRec<D>;
+#pragma unroll
+  for (int h = 0; h < R::halves; ++h) {
+    const rec_half v = *reinterpret_cast<const rec_half*>(rec + h * R::half_len + 2 * slot);
+    xq[2 * h] = v.x;
+    xq[2 * h + 1] = v.y;
+  }
+#pragma unroll
+  for (int k = 2 * R::halves; k <= D; ++k)
+    xq[k] = rec[R::tail + (k - 2 * R::halves) * kRecSlots + slot];
+}
+
+template <int D>
+__device__ __forceinline__ void rec_write(double* rec, int slot, const double (&x)[D], double d) {
+  using R = SymRec<D>;
+  double r[D + 1];
+#pragma unroll
+  for (int k = 0; k < D; ++k) r[k] = x[k];
+  r[D] = d;
+#pragma unroll
+  for (int h = 0; h < R::halves; ++h) {
+    rec_half v;
+    v.x = r[2 * h];
+    v.y = r[2 * h + 1];
+    *reinterpret_cast<rec_half*>(rec + h * R::half_len + 2 * slot) = v;
+  }
+#pragma unroll
+  for (int k = 2 * R::halves; k <= D; ++k)
+    rec[R::tail + (k - 2 * R::halves) * kRecSlots + slot] = r[k];
+}
 
 // Compiler barrier between two steps: the next step's reads of the column ring
 // must stay after this step's writes (different slots for one lane, the same slot
@@ -107,8 +163,7 @@ __device__ __forceinline__ void col_step(int sg, int lane, int coff, const doubl
   const int p = q & (kSymRing - 1);
   const int pc = coff + q;
   double xq[D + 1], c[D];
-#pragma unroll
-  for (int k = 0; k <= D; ++k) xq[k] = rec[k * kRecSlots + p];
+  rec_read<D>(rec, p, xq);
 #pragma unroll
   for (int k = 0; k < D; ++k) c[k] = col[k * kColSlots + pc];
   if (DIAG && q == lane) {  // column q = this lane's row: its sum so far is the row's
@@ -147,38 +202,55 @@ __device__ __forceinline__ void col_steps(bool fast, int s0, int s1, int lane, i
 
 // The 64 steps of a full column tile tt >= 2 in the shared-reciprocal domain (the
 // bulk of every sweep): eight blocks of eight steps, every LDS access an immediate
-// offset from a per-block base, the same code in odd and even tiles.  No prefetch of
-// the next step's records into a second register set: the other waves of the SIMD
-// hide the LDS latency, and the kernel must stay within 120 VGPRs (see
-// faml_sym_repulse).  The terms use the detect-then-fix denominators (ge_pair.hpp
+// offset from a per-block base, the same code in odd and even tiles.
+// AHEAD (round 17): the record of step j + 1 is read during step j into a second
+// register set (the sets rotate over the unrolled block, no moves), so a step's
+// e = x_i - x_j waits for no LDS round trip; the ring is not written during the tile,
+// only the step's compiler barrier and the registers stood in the way.  The first
+// record is read here, after the caller's staging wave_lds_sync.  The read issued in the
+// 64th step points at the slot behind the tile (at most slot 191: inside the ring),
+// which the next tile stages later: its value is dropped, the next call reads its own
+// first record afresh (the drain and the tiles tt < 2 run col_step, which reads its own).
+// The kernel must stay within 120 VGPRs (see faml_sym_repulse): SymAhead says which
+// dimensions can afford the second set (D = 4, at 117 without it, cannot).
+// The terms use the detect-then-fix denominators (ge_pair.hpp
 // pair_den_detect): in these tiles every row is a member and no lane meets its own
 // row, so a step takes the fix-up only for members closer than eps (a short last
 // tile's padding sits at the origin), or an all-ones low word of the distance.
 // STAMP: `fixes` counts the steps that took it.
-template <int D, bool REPEL_ONE, bool STAMP>
+template <int D>
+struct SymAhead {
+#ifdef GE_SYM_AHEAD  // tuning switch (scripts/build_variant.sh): 0 = the halves alone
+  static constexpr bool v = GE_SYM_AHEAD != 0 && D <= 3;
+#else
+  static constexpr bool v = D <= 3;
+#endif
+};
+
+template <int D, bool REPEL_ONE, bool STAMP, bool AHEAD>
 __device__ __forceinline__ void tile_steps(int tt, int lane, const double* rec, double* col,
                                            const double (&xr)[D], double dr, double repel,
                                            double (&racc)[D], int& fixes) {
-  const double* rb = rec + ((64 * tt - lane) & (kSymRing - 1));
+  const int pb = (64 * tt - lane) & (kSymRing - 1);
   double* cb = col + kColBase - lane;
-  // second record base for the components from 2 on: with it every record read of a
-  // step is an immediate offset (ds_read2_b64 reaches 255 slots)
-  int o2 = 2 * kRecSlots;
-  asm volatile("" : "+v"(o2));  // opaque: folded back, the offset would need the add again
-  const double* rb2 = rb + o2;
+  double xn[D + 1];
+  if (AHEAD) rec_read<D>(rec, pb, xn);
   for (int j0 = 0; j0 < 64; j0 += 8) {
-    const double* rj = rb + j0;
-    const double* rj2 = rb2 + j0;
+    const int pj = pb + j0;
     double* cj = cb + j0;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
       double* cp = cj + jj;
       double c[D], xq[D + 1];
+      if (AHEAD) {
 #pragma unroll
-      for (int k = 0; k <= D; ++k)
-        xq[k] = (D >= 3 && k >= 2) ? rj2[(k - 2) * kRecSlots + jj] : rj[k * kRecSlots + jj];
+        for (int k = 0; k <= D; ++k) xq[k] = xn[k];
+      } else {
+        rec_read<D>(rec, pj + jj, xq);
+      }
 #pragma unroll
       for (int k = 0; k < D; ++k) c[k] = cp[k * kColSlots];
+      if (AHEAD) rec_read<D>(rec, pj + jj + 1, xn);  // the next step's, used behind the barrier
       double t[D];
       bool fixed = false;
       rep_term<D, true, REPEL_ONE, true>(xr, xq, dr, xq[D], repel, t, &fixed);
@@ -458,16 +530,10 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
     }
     const int cb = kColBase;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-      rec[k * kRecSlots + p] = xc[k];
+    for (int k = 0; k < D; ++k)
       col[k * kColSlots + cb + lane] = ic[k];  // the column enters with its sum so far
-    }
-    rec[D * kRecSlots + p] = dc;
-    if (!(tt & 1)) {  // slots 0..63 are mirrored at 128..191
-#pragma unroll
-      for (int k = 0; k < D; ++k) rec[k * kRecSlots + p + kSymRing] = xc[k];
-      rec[D * kRecSlots + p + kSymRing] = dc;
-    }
+    rec_write<D>(rec, p, xc, dc);
+    if (!(tt & 1)) rec_write<D>(rec, p + kSymRing, xc, dc);  // slots 0..63 mirrored at 128..191
     wave_lds_sync();
     const bool raised = sweep_prio(spun, lead);  // for the tile's 64 steps
     if (STAMP) hint[0] += raised;
@@ -478,7 +544,8 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
       col_steps<D, REPEL_ONE, true>(fast, 64 * tt, 64 * tt + 64, lane, coff, rec, col, xr, dr,
                                     repel, racc);
     else if (fast)
-      tile_steps<D, REPEL_ONE, STAMP>(tt, lane, rec, col, xr, dr, repel, racc, hint[2]);
+      tile_steps<D, REPEL_ONE, STAMP, SymAhead<D>::v>(tt, lane, rec, col, xr, dr, repel, racc,
+                                                      hint[2]);
     else
       col_steps<D, REPEL_ONE, false>(false, 64 * tt, 64 * tt + 64, lane, coff, rec, col, xr, dr,
                                      repel, racc);
@@ -488,11 +555,11 @@ __device__ __forceinline__ void sweep_unit(int lane, int A, int base, int s, int
   }
   {  // drain: the last columns cross the wave; the slots past them hold inert records
     const int p = (64 * ntiles + lane) & (kSymRing - 1);
+    double zero[D];
 #pragma unroll
-    for (int k = 0; k <= D; ++k) {
-      rec[k * kRecSlots + p] = 0.0;
-      if (!(ntiles & 1)) rec[k * kRecSlots + p + kSymRing] = 0.0;
-    }
+    for (int k = 0; k < D; ++k) zero[k] = 0.0;
+    rec_write<D>(rec, p, zero, 0.0);
+    if (!(ntiles & 1)) rec_write<D>(rec, p + kSymRing, zero, 0.0);
     // the drain is tile ntiles: the last tile moves down to 0..63
 #pragma unroll
     for (int k = 0; k < D; ++k) col[k * kColSlots + lane] = col[k * kColSlots + kColBase + lane];

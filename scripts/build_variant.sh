@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a tuning variant of libge.so with extra -D flags (kernel knobs such as
-# GE_TILE_CAP, GE_TILE_ROWS, GE_ROWS_MINBLOCKS, GE_BAR_ORDER) into
+# GE_TILE_CAP, GE_TILE_ROWS, GE_ROWS_MINBLOCKS, GE_BAR_ORDER, GE_SYM_AHEAD, GE_SYM_HALVES4) into
 # graph-embed_amd/variants/NAME/.  ONLY="ge_fa ge_faml" recompiles just those
 # sources with the flags and links the main build's objects for the rest.
 # Load it with GE_LIB_PATH=graph-embed_amd/variants/NAME/libge.so (tuning only).
