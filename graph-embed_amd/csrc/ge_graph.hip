@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "ge_internal.hpp"
@@ -166,7 +167,21 @@ __global__ void lcc_copy_kernel(int n, const int* __restrict__ ip, const int* __
 
 // Library calls (rocPRIM sort / scan) on at most this many items each: the C5
 // generator has 1.6e9 directed draws, which is past what one call is trusted with.
-constexpr long long kChunk = 1ll << 28;
+// GE_GRAPH_CHUNK sets a smaller count, so that small inputs take the chunked paths.
+constexpr long long kChunkMax = 1ll << 28;
+
+// Read once per entry call; the call's census (ge_graph_info) starts over.
+void begin_graph_call(ge_ctx* ctx) {
+  long long chunk = kChunkMax;
+  if (const char* e = std::getenv("GE_GRAPH_CHUNK")) {
+    char* end = nullptr;
+    chunk = std::strtoll(e, &end, 10);
+    GE_REQUIRE(end != e && *end == 0 && chunk >= 1 && chunk <= kChunkMax,
+               "GE_GRAPH_CHUNK must be an item count in 1 .. 2^28");
+  }
+  ctx->graph = {};
+  ctx->graph.chunk = chunk;
+}
 
 // carry[c + 1] = carry[c] + the total of chunk c (its local exclusive scan's last
 // value + its last input), before the chunk is shifted
@@ -182,18 +197,23 @@ __global__ void add_carry_kernel(long long len, int* __restrict__ out,
 }
 
 template <class T>
-void exclusive_scan(hipStream_t st, const T* in, T* out, long long count) {
-  if (count <= kChunk) {
+void exclusive_scan(ge_ctx* ctx, const T* in, T* out, long long count) {
+  hipStream_t st = ctx->stream;
+  const long long chunk = ctx->graph.chunk;
+  ctx->graph.scans += 1;
+  if (count <= chunk) {
     prim_exclusive_sum(st, in, out, (size_t)count);
+    ctx->graph.scan_calls += 1;
     return;
   }
-  // chunks of kChunk, each shifted by the running total of the ones before
+  // chunks of `chunk` items, each shifted by the running total of the ones before
   static_assert(sizeof(T) == sizeof(int), "chunked scan of int counts");
-  const int nc = (int)((count + kChunk - 1) / kChunk);
+  const int nc = (int)((count + chunk - 1) / chunk);
+  ctx->graph.scan_calls += nc;
   DevBuf<int> carry(nc + 1);
   GE_HIP(hipMemsetAsync(carry.p, 0, sizeof(int) * (nc + 1), st));
   for (int c = 0; c < nc; ++c) {
-    const long long c0 = c * kChunk, len = std::min(kChunk, count - c0);
+    const long long c0 = c * chunk, len = std::min(chunk, count - c0);
     prim_exclusive_sum(st, in + c0, out + c0, (size_t)len);
     hipLaunchKernelGGL(chunk_total_kernel, dim3(1), dim3(1), 0, st,
                        (const int*)(out + c0 + len - 1), (const int*)(in + c0 + len - 1), carry.p, c);
@@ -203,7 +223,7 @@ void exclusive_scan(hipStream_t st, const T* in, T* out, long long count) {
 }
 
 // Valid keys per row (duplicates included), to cut the keys into row ranges of at
-// most kChunk for the sort.
+// most a chunk for the sort.
 __global__ void key_rows_kernel(long long L, long long n, const u64* __restrict__ k,
                                 int* __restrict__ rowcnt) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -241,6 +261,7 @@ struct DCsr {
 
 void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
   hipStream_t st = ctx->stream;
+  const long long chunk = ctx->graph.chunk;
   int scale = 1;
   while ((1ll << scale) < n) ++scale;
   long long L = 2 * draws;
@@ -250,13 +271,15 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
     hipLaunchKernelGGL(rmat_keys_kernel, dim3(grid_for(draws)), dim3(256), 0, st, draws, scale,
                        (long long)n, splitmix64_host(seed), k.p);
   GE_HIP(hipGetLastError());
-  if (L <= kChunk) {
+  if (L == 0) {
+    // no draws: nothing to sort, flag or emit (an empty grid is a launch error)
+  } else if (L <= chunk) {
     const size_t tmp = prim_sort_keys_bytes(st, k.p, k2.p, (size_t)L, 64);
     DevBuf<unsigned char> scratch(tmp);
     // all 64 bits: the kNoKey sentinel sorts last
     prim_sort_keys(st, scratch.p, tmp, k.p, k2.p, (size_t)L, 64);
   } else {
-    // Large inputs: cut the valid keys into row ranges of at most kChunk keys
+    // Large inputs: cut the valid keys into row ranges of at most chunk keys
     // (row = key / n, so ranges of rows are ranges of keys), scatter each into its
     // segment and sort the segments one by one -- the concatenation is sorted; the
     // invalid keys are dropped here instead of sorting last.
@@ -271,8 +294,8 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
     std::vector<long long> boff{0};
     long long acc = 0, tot = 0;
     for (int r = 0; r < n; ++r) {
-      GE_REQUIRE(h_rc[r] <= kChunk, "device R-MAT: one row exceeds a sort chunk");
-      if (acc + h_rc[r] > kChunk) {
+      GE_REQUIRE(h_rc[r] <= chunk, "device R-MAT: one row exceeds a sort chunk");
+      if (acc + h_rc[r] > chunk) {
         bound.push_back(r);
         boff.push_back(tot);
         acc = 0;
@@ -281,6 +304,7 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
       tot += h_rc[r];
     }
     const int nb = (int)bound.size();
+    ctx->graph.sort_segments = nb;
     DevBuf<int> d_bound(nb), d_fill(nb);
     DevBuf<long long> d_boff(nb);
     d_bound.upload(bound.data(), nb, st);
@@ -289,7 +313,14 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
     hipLaunchKernelGGL(scatter_keys_kernel, dim3(grid_for(L)), dim3(256), 0, st, L, (long long)n,
                        nb, d_bound.p, d_boff.p, d_fill.p, k.p, k2.p);
     GE_HIP(hipGetLastError());
-    const size_t tmp = prim_sort_keys_bytes(st, k2.p, k.p, (size_t)kChunk, 64);
+    // one scratch buffer for the largest need (the library picks its algorithm by
+    // size, so a shorter segment may ask for more than a longer one)
+    size_t tmp = 1;
+    for (int b = 0; b < nb; ++b) {
+      const long long b0 = boff[b], b1 = b + 1 < nb ? boff[b + 1] : tot;
+      if (b1 > b0)
+        tmp = std::max(tmp, prim_sort_keys_bytes(st, k2.p + b0, k.p + b0, (size_t)(b1 - b0), 64));
+    }
     DevBuf<unsigned char> scratch(tmp);
     for (int b = 0; b < nb; ++b) {
       const long long b0 = boff[b], b1 = b + 1 < nb ? boff[b + 1] : tot;
@@ -300,8 +331,10 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
     L = tot;
   }
   DevBuf<int> f(std::max(L, 1ll)), pos(std::max(L, 1ll));
-  hipLaunchKernelGGL(unique_flags_kernel, dim3(grid_for(L)), dim3(256), 0, st, L, k2.p, f.p);
-  exclusive_scan(st, f.p, pos.p, L);
+  if (L > 0) {  // (every key of a chunked call may have been invalid)
+    hipLaunchKernelGGL(unique_flags_kernel, dim3(grid_for(L)), dim3(256), 0, st, L, k2.p, f.p);
+    exclusive_scan(ctx, f.p, pos.p, L);
+  }
   const long long nnz = L ? (long long)read_back(pos.p + (L - 1), st) + read_back(f.p + (L - 1), st) : 0;
   out.n = n;
   out.nnz = nnz;
@@ -310,9 +343,10 @@ void rmat_device(ge_ctx* ctx, int n, long long draws, u64 seed, DCsr& out) {
   out.ip.alloc(n + 1);
   DevBuf<int> cnt(n + 1);
   GE_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * (n + 1), st));
-  hipLaunchKernelGGL(emit_csr_kernel, dim3(grid_for(L)), dim3(256), 0, st, L, (long long)n, k2.p,
-                     f.p, pos.p, out.ix.p, cnt.p);
-  exclusive_scan(st, cnt.p, out.ip.p, n + 1);
+  if (L > 0)
+    hipLaunchKernelGGL(emit_csr_kernel, dim3(grid_for(L)), dim3(256), 0, st, L, (long long)n, k2.p,
+                       f.p, pos.p, out.ix.p, cnt.p);
+  exclusive_scan(ctx, cnt.p, out.ip.p, n + 1);
   fill_ones(out.dx.p, nnz, st);  // unit weights
   GE_HIP(hipGetLastError());
 }
@@ -346,14 +380,14 @@ void lcc_device(ge_ctx* ctx, const DCsr& A, DCsr& out) {
   hipLaunchKernelGGL(comp_size_kernel, dim3(grid_for(n)), dim3(256), 0, st, n, lab.p, size.p);
   hipLaunchKernelGGL(best_comp_kernel, dim3(grid_for(n)), dim3(256), 0, st, n, size.p, best.p);
   hipLaunchKernelGGL(member_kernel, dim3(grid_for(n)), dim3(256), 0, st, n, lab.p, best.p, keep.p);
-  exclusive_scan(st, keep.p, newid.p, n);
+  exclusive_scan(ctx, keep.p, newid.p, n);
   const int k = read_back(newid.p + (n - 1), st) + read_back(keep.p + (n - 1), st);
   GE_HIP(hipMemsetAsync(len.p, 0, sizeof(int) * (n + 1), st));
   hipLaunchKernelGGL(lcc_rows_kernel, dim3(grid_for(n)), dim3(256), 0, st, n, A.ip.p, keep.p,
                      newid.p, len.p);
   out.n = k;
   out.ip.alloc(k + 1);
-  exclusive_scan(st, len.p, out.ip.p, k + 1);
+  exclusive_scan(ctx, len.p, out.ip.p, k + 1);
   out.nnz = read_back(out.ip.p + k, st);
   out.ix.alloc(std::max(out.nnz, 1ll));
   out.dx.alloc(std::max(out.nnz, 1ll));
@@ -384,6 +418,7 @@ int ge_rmat_csr_device(ge_ctx* ctx, int n, long long draws, unsigned long long s
   return ge::guarded([&] {
     GE_REQUIRE(ctx && out && n > 1 && draws >= 0, "bad R-MAT arguments");
     ge::DeviceGuard g(ctx);
+    ge::begin_graph_call(ctx);
     ge::DCsr A;
     ge::rmat_device(ctx, n, draws, seed, A);
     auto* h = new ge_csr();
@@ -408,6 +443,7 @@ int ge_largest_component_device(ge_ctx* ctx, int n, const int* ip, const int* ix
   return ge::guarded([&] {
     GE_REQUIRE(ctx && out && n >= 0 && (n == 0 || (ip && ix && dx)), "bad arguments");
     ge::DeviceGuard g(ctx);
+    ge::begin_graph_call(ctx);
     hipStream_t st = ctx->stream;
     ge::DCsr A;
     A.n = n;

@@ -621,10 +621,16 @@ int ge_interpolation_matrix(int num_cols, int num_rows, const int* offsets, cons
 
 int ge_ptap(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, int m,
             const int* pip, const int* pix, ge_csr** out) {
+  return ge_ptap_rows(ctx, n, ip, ix, dx, m, pip, pix, 0, m, out);
+}
+
+int ge_ptap_rows(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, int m,
+                 const int* pip, const int* pix, int a0, int a1, ge_csr** out) {
   return guarded([&] {
     GE_REQUIRE(ctx && out && pip && pix, "null argument");
     ge::check_csr(n, ip, ix, dx);
     GE_REQUIRE(m >= 0 && pip[0] == 0 && pip[m] == n, "P_T must have one entry per fine vertex");
+    GE_REQUIRE(0 <= a0 && a0 <= a1 && a1 <= m, "P^T A P: row range outside [0, m]");
     ge::DeviceGuard g(ctx);
     hipStream_t s = ctx->stream;
     auto* c = new ge_csr();
@@ -633,12 +639,44 @@ int ge_ptap(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, 
       ge::DevBuf<int> dpip(m + 1), dpix(std::max(n, 1));
       dpip.upload(pip, m + 1, s);
       dpix.upload(pix, n, s);
-      ge::ptap_device(ctx, n, A.ip.p, A.ix.p, A.dx.p, A.nnz, m, pip, dpip.p, dpix.p, 0, m, c);
+      ge::ptap_device(ctx, n, A.ip.p, A.ix.p, A.dx.p, A.nnz, m, pip, dpip.p, dpix.p, a0, a1, c);
     } catch (...) {
       delete c;
       throw;
     }
     *out = c;
+  });
+}
+
+int ge_ptap_info(const ge_ctx* ctx, int* bn, int* bb, int* ba, int* sort, long long* entries,
+                 long long* runs) {
+  return guarded([&] {
+    GE_REQUIRE(ctx && bn && bb && ba && sort && entries && runs, "null argument");
+    *bn = ctx->ptap.bn;
+    *bb = ctx->ptap.bb;
+    *ba = ctx->ptap.ba;
+    *sort = ctx->ptap.split;
+    *entries = ctx->ptap.entries;
+    *runs = ctx->ptap.runs;
+  });
+}
+
+int ge_graph_info(const ge_ctx* ctx, long long* chunk, int* sort_segments, int* scans,
+                  int* scan_calls) {
+  return guarded([&] {
+    GE_REQUIRE(ctx && chunk && sort_segments && scans && scan_calls, "null argument");
+    *chunk = ctx->graph.chunk;
+    *sort_segments = ctx->graph.sort_segments;
+    *scans = ctx->graph.scans;
+    *scan_calls = ctx->graph.scan_calls;
+  });
+}
+
+int ge_radius_info(const ge_ctx* ctx, int* rounds, int* max_pops) {
+  return guarded([&] {
+    GE_REQUIRE(ctx && rounds && max_pops, "null argument");
+    *rounds = ctx->radius.rounds;
+    *max_pops = ctx->radius.max_pops;
   });
 }
 

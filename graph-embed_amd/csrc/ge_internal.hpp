@@ -165,6 +165,19 @@ struct ge_ctx {
   int device = 0;
   hipStream_t own = nullptr;
   hipStream_t stream = nullptr;
+  // What the last call of each set-up step took (ge_ptap_info, ge_graph_info,
+  // ge_radius_info): host values the calls have anyway, kept for the tests' census.
+  struct {
+    int bn = 0, bb = 0, ba = 0, split = GE_PTAP_SORT_NONE;
+    long long entries = 0, runs = 0;
+  } ptap;
+  struct {
+    long long chunk = 0;  // items per library sort or scan call (GE_GRAPH_CHUNK)
+    int sort_segments = 0, scans = 0, scan_calls = 0;
+  } graph;
+  struct {
+    int rounds = 0, max_pops = 0;
+  } radius;
 };
 
 // A communicator (ge_dist.hip): RCCL, or a caller transport staged through host

@@ -211,6 +211,7 @@ void ptap_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const dou
   out->indptr.assign(R + 1, 0);
   out->indices.clear();
   out->data.clear();
+  ctx->ptap = {};
   const int c0 = h_pt_ip[a0], c1 = h_pt_ip[a1];
   const int P = c1 - c0;
   if (n == 0 || R == 0 || P == 0 || nnz == 0) return;
@@ -240,7 +241,14 @@ void ptap_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const dou
   GE_REQUIRE(L < (1ll << 31), "P^T A P: more than 2^31 entries in one call (shard the rows)");
 
   const int bn = bits_below(n), bb = bits_below(m), ba = bits_below(R);
-  const bool split = ba + bb + bn > 64 || std::getenv("GE_PTAP_SPLIT_SORT") != nullptr;
+  const bool wide = ba + bb + bn > 64;
+  const bool split = wide || std::getenv("GE_PTAP_SPLIT_SORT") != nullptr;
+  ctx->ptap.bn = bn;
+  ctx->ptap.bb = bb;
+  ctx->ptap.ba = ba;
+  ctx->ptap.split = wide ? GE_PTAP_SORT_SPLIT_WIDTH
+                         : split ? GE_PTAP_SORT_SPLIT_OVERRIDE : GE_PTAP_SORT_SINGLE;
+  ctx->ptap.entries = L;
   DevBuf<u64> k(L), k2(L);
   DevBuf<double> v(L), v2(L);
   u64 *kp = k.p, *kq = k2.p;
@@ -297,6 +305,7 @@ void ptap_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const dou
   int nc = 0;
   GE_HIP(hipMemcpyAsync(&nc, runid.p + (L - 1), sizeof(int), hipMemcpyDeviceToHost, st));
   GE_HIP(hipStreamSynchronize(st));
+  ctx->ptap.runs = nc;
   out->indices.resize(nc);
   out->data.resize(nc);
   GE_HIP(hipMemcpyAsync(out->indptr.data(), indptr.p, sizeof(int) * (R + 1),

@@ -148,7 +148,8 @@ __global__ void pop_kernel(int nl, int round, const int* __restrict__ live,
                            const double* __restrict__ et, const u64* __restrict__ best_t,
                            const u64* __restrict__ best_ij, double* __restrict__ r,
                            int* __restrict__ asg_round, double* __restrict__ asg_t,
-                           u64* __restrict__ asg_ij, int* __restrict__ popped) {
+                           u64* __restrict__ asg_ij, int* __restrict__ popped,
+                           int* __restrict__ pops) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nl) return;
   const int e = live[q];
@@ -163,6 +164,7 @@ __global__ void pop_kernel(int nl, int round, const int* __restrict__ live,
                      (!lj || (best_t[j] == o && best_ij[j] == ij));
   if (!ready) return;
   popped[e] = round;
+  atomicAdd(pops, 1);  // census only (ge_radius_info); read back with the next live count
   const double d = -t;
   if (li) {
     r[i] = d;
@@ -262,6 +264,7 @@ bool radius_step_device(ge_ctx* ctx, int m, double* cA, double* rA, int dim, boo
                         const int* AcI, const int* AcJ) {
   hipStream_t s = ctx->stream;
   std::fill(rA, rA + m, 0.0);
+  ctx->radius = {};
   if (m == 0) return true;
   DevBuf<double> X((size_t)m * dim), r(m);
   X.upload(cA, (size_t)m * dim, s);
@@ -323,7 +326,7 @@ bool radius_step_device(ge_ctx* ctx, int m, double* cA, double* rA, int dim, boo
   if (has_zero) return false;  // coincident coordinates: the host replays the serial loop
 
   if (E > 0) {
-    DevBuf<int> la(E), lb(E), popped(E), asg_round(m), next_count(1);
+    DevBuf<int> la(E), lb(E), popped(E), asg_round(m), next_count(2);  // {next live, pops}
     DevBuf<u64> best_t(m), best_ij(m), asg_ij(m);
     DevBuf<double> asg_t(m);
     GE_HIP(hipMemsetAsync(popped.p, 0xff, sizeof(int) * E, s));
@@ -336,18 +339,23 @@ bool radius_step_device(ge_ctx* ctx, int m, double* cA, double* rA, int dim, boo
       GE_REQUIRE(round <= E, "radius step: no progress");
       GE_HIP(hipMemsetAsync(best_t.p, 0, sizeof(u64) * m, s));
       GE_HIP(hipMemsetAsync(best_ij.p, 0, sizeof(u64) * m, s));
-      GE_HIP(hipMemsetAsync(next_count.p, 0, sizeof(int), s));
+      GE_HIP(hipMemsetAsync(next_count.p, 0, sizeof(int) * 2, s));
       const dim3 g(grid_for(nl)), b(256);
       hipLaunchKernelGGL(best_time_kernel, g, b, 0, s, nl, live, ei.p, ej.p, et.p, r.p, best_t.p);
       hipLaunchKernelGGL(best_pair_kernel, g, b, 0, s, nl, live, ei.p, ej.p, et.p, r.p, best_t.p,
                          best_ij.p);
       hipLaunchKernelGGL(pop_kernel, g, b, 0, s, nl, round, live, ei.p, ej.p, et.p, best_t.p,
-                         best_ij.p, r.p, asg_round.p, asg_t.p, asg_ij.p, popped.p);
+                         best_ij.p, r.p, asg_round.p, asg_t.p, asg_ij.p, popped.p,
+                         next_count.p + 1);
       hipLaunchKernelGGL(shift_kernel, g, b, 0, s, nl, round, live, ei.p, ej.p, et.p, r.p,
                          asg_round.p, asg_t.p, asg_ij.p, popped.p, next, next_count.p);
       GE_HIP(hipGetLastError());
-      GE_HIP(hipMemcpyAsync(&nl, next_count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      int got[2] = {0, 0};
+      GE_HIP(hipMemcpyAsync(got, next_count.p, sizeof(int) * 2, hipMemcpyDeviceToHost, s));
       GE_HIP(hipStreamSynchronize(s));
+      nl = got[0];
+      ctx->radius.rounds = round + 1;
+      ctx->radius.max_pops = std::max(ctx->radius.max_pops, got[1]);
       std::swap(live, next);
     }
   }

@@ -109,6 +109,12 @@ _SIGS = {
                                                ctypes.POINTER(_vp)]),
     "ge_ptap": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int, _i32p,
                                _i32p, ctypes.POINTER(_vp)]),
+    "ge_ptap_rows": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int, _i32p,
+                                    _i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "ge_ptap_info": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_longlong),
+                                    ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_graph_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong), _ip, _ip, _ip]),
+    "ge_radius_info": (ctypes.c_int, [_vp, _ip, _ip]),
     "ge_csr_shape": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_longlong)]),
     "ge_csr_copy": (ctypes.c_int, [_vp, _i32p, _vp, _vp]),
     "ge_csr_free": (ctypes.c_int, [_vp]),
@@ -347,14 +353,40 @@ class Context:
                                           _vp(t[3].data_ptr()), ctypes.byref(q)))
         return q.value
 
-    def ptap(self, A, PT):
+    def ptap(self, A, PT, rows=None):
+        """P_T A P_T^T; rows=(a0, a1): coarse rows [a0, a1) only (ge_ptap_rows)."""
         ip, ix, dx = _csr(A)
         pip = np.ascontiguousarray(PT[0], dtype=np.int32)
         pix = np.ascontiguousarray(PT[1], dtype=np.int32)
         h = _vp()
-        _check(lib().ge_ptap(self.h, len(ip) - 1, ip, ix, dx, len(pip) - 1, pip, pix,
-                             ctypes.byref(h)))
+        if rows is None:
+            _check(lib().ge_ptap(self.h, len(ip) - 1, ip, ix, dx, len(pip) - 1, pip, pix,
+                                 ctypes.byref(h)))
+        else:
+            _check(lib().ge_ptap_rows(self.h, len(ip) - 1, ip, ix, dx, len(pip) - 1, pip, pix,
+                                      rows[0], rows[1], ctypes.byref(h)))
         return _take_csr(h)
+
+    def ptap_info(self):
+        """ge_ptap_info of the last P^T A P call on this context: key widths bn, bb, ba,
+        sort (one of PTAP_SORT_*), emitted entries and (row, column) runs."""
+        v = [ctypes.c_int() for _ in range(4)] + [ctypes.c_longlong(), ctypes.c_longlong()]
+        _check(lib().ge_ptap_info(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("bn", "bb", "ba", "sort", "entries", "runs"), (x.value for x in v)))
+
+    def graph_info(self):
+        """ge_graph_info of the last rmat_csr / largest_component on this context."""
+        c = ctypes.c_longlong()
+        v = [ctypes.c_int() for _ in range(3)]
+        _check(lib().ge_graph_info(self.h, ctypes.byref(c), *[ctypes.byref(x) for x in v]))
+        return dict(chunk=c.value, sort_segments=v[0].value, scans=v[1].value,
+                    scan_calls=v[2].value)
+
+    def radius_info(self):
+        """ge_radius_info of the last radius_step on this context: (rounds, max pops in one)."""
+        r, p = ctypes.c_int(), ctypes.c_int()
+        _check(lib().ge_radius_info(self.h, ctypes.byref(r), ctypes.byref(p)))
+        return r.value, p.value
 
     def embed(self, As, hier, dim, base_iterations=100000, ml_iterations=100,
               print_progress=False, **kw):
@@ -870,6 +902,8 @@ def _take_csr(h):
 # -- host-resident entry points (no device needed) ----------------------------
 
 PATH_HOST, PATH_DEVICE_EXACT, PATH_DEVICE_ORDERED = 0, 1, 2  # GE_PARTITION_PATH_*
+# GE_PTAP_SORT_*
+PTAP_SORT_NONE, PTAP_SORT_SINGLE, PTAP_SORT_SPLIT_WIDTH, PTAP_SORT_SPLIT_OVERRIDE = 0, 1, 2, 3
 
 
 # ge_partition_census (include/ge.h), in declaration order

@@ -452,6 +452,23 @@ int ge_interpolation_matrix(int num_cols, int num_rows, const int* offsets,
  * examples/embedder.cpp:213-216; linalgcpp).  Output rows sorted ascending. */
 int ge_ptap(ge_ctx* ctx, int n, const int* indptr, const int* indices, const double* data,
             int m, const int* pt_indptr, const int* pt_indices, ge_csr** out);
+/* Coarse rows [a0, a1) of the same product, 0 <= a0 <= a1 <= m: a1 - a0 rows of m
+ * columns (the row-range form that ge_ptap_dist gives each rank its share with). */
+int ge_ptap_rows(ge_ctx* ctx, int n, const int* indptr, const int* indices, const double* data,
+                 int m, const int* pt_indptr, const int* pt_indices, int a0, int a1,
+                 ge_csr** out);
+/* What the last P^T A P call on ctx did (ge_ptap, ge_ptap_rows, a rank's share of
+ * ge_ptap_dist): the key widths in bits of j (bn), of the column aggregate (bb) and
+ * of the row (ba), which sort ran, the emitted entries and the (row, column) runs.
+ * GE_PTAP_SORT_NONE: the call returned before sorting (nothing to emit). */
+enum {
+  GE_PTAP_SORT_NONE = 0,
+  GE_PTAP_SORT_SINGLE = 1,         /* one sort of the composite key, <= 64 bits */
+  GE_PTAP_SORT_SPLIT_WIDTH = 2,    /* split sort: the key needs more than 64 bits */
+  GE_PTAP_SORT_SPLIT_OVERRIDE = 3  /* split sort by GE_PTAP_SPLIT_SORT alone */
+};
+int ge_ptap_info(const ge_ctx* ctx, int* bn, int* bb, int* ba, int* sort, long long* entries,
+                 long long* runs);
 int ge_csr_shape(const ge_csr* c, int* rows, int* cols, long long* nnz);
 int ge_csr_copy(const ge_csr* c, int* indptr, int* indices, double* data);
 int ge_csr_free(ge_csr* c);
@@ -497,6 +514,10 @@ int ge_radius_step_device(ge_ctx* ctx, int m, double* coords_A, double* r_A, int
                           int coarse_is_base, int mc, const int* ptc_indptr,
                           const int* ptc_indices, const double* coords_Ac, const double* r_Ac,
                           const int* ac_indptr, const int* ac_indices, int* used_device);
+/* The device rounds of the last ge_radius_step_device on ctx: how many ran and the
+ * largest number of events popped in one of them (both 0 when no round ran: no
+ * events, or the host loop ran instead). */
+int ge_radius_info(const ge_ctx* ctx, int* rounds, int* max_pops);
 
 /* ---- multi-GPU: one process per GPU, a communicator per context ----
  * The reference has no multi-GPU path (it is OpenMP on one node); these entry
@@ -654,6 +675,12 @@ int ge_rmat_csr_device(ge_ctx* ctx, int n, long long draws, unsigned long long s
                        ge_csr** out);
 int ge_largest_component_device(ge_ctx* ctx, int n, const int* indptr, const int* indices,
                                 const double* data, ge_csr** out);
+/* The last of these two calls on ctx: the items per library sort or scan call
+ * (GE_GRAPH_CHUNK, default 2^28), the row-range segments the R-MAT keys were sorted
+ * in (0: one sort of all keys), the scans it ran and the library calls they took
+ * (scan_calls > scans: a scan ran in chunks). */
+int ge_graph_info(const ge_ctx* ctx, long long* chunk, int* sort_segments, int* scans,
+                  int* scan_calls);
 
 #ifdef __cplusplus
 }
