@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "ge_faml_sched.hpp"
+#include "ge_far.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
 #include "ge_rows.hpp"
@@ -867,6 +868,12 @@ struct ge_faml_plan {
   bool fast = false;
   ge::DevBuf<int4> fitems;  // (aggregate, first row, end row, 0), descending work
   int nfitems = 0, fast_blocks = 0;
+  // FARFIELD mode (ge_far.hip, the segmented engine): the streamed whole aggregates of
+  // at least far_min_ml members, larger first; the other streamed rows are FAST items
+  ge::FarSegEngine* far = nullptr;
+  int far_reason = GE_FAR_NOT_REQUESTED, far_min_ml = 0;
+  double theta = 0.5;
+  std::vector<int> faraggs;
   // symmetric repulsion (ge_sym.hpp): sweep units and per-tile progress counters
   bool sym = false;
   bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
@@ -948,9 +955,33 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   const int dim = pl->dim, n = pl->n;
   const int cus = device_cus();
   const int nranks = pl->comm ? pl->comm->nranks : 1;
-  const FamlSched s = faml_schedule(faml_sched_in(h_pt_ip, aggs, split,
-                                                  pl->comm ? pl->comm->rank : 0, nranks, dim,
-                                                  pl->mode, cus, sym_occupancy(dim)));
+  FamlSchedIn sin = faml_sched_in(h_pt_ip, aggs, split, pl->comm ? pl->comm->rank : 0, nranks,
+                                  dim, pl->mode, cus, sym_occupancy(dim));
+  FamlSched s = faml_schedule(sin);
+  pl->far_min_ml = sin.knobs.far_min_ml;
+  bool dp_done = false;
+  if (pl->mode == GE_MODE_FARFIELD) {
+    // every internal deg + 1 of the streamed rows must be a mass: checked once, here
+    pl->far_reason = sin.wide || dim > kNarrowMaxDim ? GE_FAR_DIM
+                     : s.faraggs.empty()            ? GE_FAR_SMALL
+                                                    : GE_FAR_ACTIVE;
+    if (pl->far_reason == GE_FAR_ACTIVE) {
+      pl->irows.alloc(s.irows.size());
+      pl->irows.upload(s.irows.data(), s.irows.size(), st);
+      pl->DP.alloc(n);
+      hipLaunchKernelGGL(faml_huge_dp, dim3(((int)s.irows.size() + kHT - 1) / kHT), dim3(kHT), 0,
+                         st, (int)s.irows.size(), pl->irows.p, pl->pt_ix, pl->vA, pl->ip, pl->ix,
+                         pl->dx, pl->DP.p, pl->c.use_weights);
+      GE_HIP(hipGetLastError());
+      dp_done = true;
+      if (!far_masses_ok_rows(st, (int)s.irows.size(), pl->irows.p, pl->DP.p)) {
+        pl->far_reason = GE_FAR_MASS;  // the whole plan runs FAST
+        sin.mode = GE_MODE_FAST;
+        s = faml_schedule(sin);
+      }
+    }
+  }
+  pl->faraggs = s.faraggs;
   pl->res_cap = s.res_cap;
   std::copy(s.census, s.census + 4, pl->census);
   pl->off_m = s.off_m;
@@ -1034,8 +1065,10 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   pl->items.alloc(std::max<size_t>(s.items.size(), 1));
   pl->queue.alloc(std::max(pl->iterations, 1));
   pl->huge.alloc(std::max<size_t>(s.huge.size(), 1));
-  pl->irows.alloc(std::max<size_t>(s.irows.size(), 1));
-  pl->irows.upload(s.irows.data(), s.irows.size(), st);
+  if (!dp_done) {
+    pl->irows.alloc(std::max<size_t>(s.irows.size(), 1));
+    pl->irows.upload(s.irows.data(), s.irows.size(), st);
+  }
   pl->order.upload(s.order.data(), s.order.size(), st);
   pl->beg.upload(s.beg.data(), s.beg.size(), st);
   pl->rows.upload(s.rows.data(), s.rows.size(), st);
@@ -1059,7 +1092,17 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
   if (pl->nirows > 0) {
     pl->Xa.alloc((size_t)n * dim);
     pl->Xb.alloc((size_t)n * dim);
-    pl->DP.alloc(n);
+    if (!dp_done) pl->DP.alloc(n);
+  }
+  if (!pl->faraggs.empty()) {  // items of 64 rows unless GE_FAR_R=4 (256), as on the single level
+    std::vector<int> base, size;
+    for (int a : pl->faraggs) {
+      base.push_back(h_pt_ip[a]);
+      size.push_back(h_pt_ip[a + 1] - h_pt_ip[a]);
+    }
+    int item_rows = kFarLeaf;
+    if (const char* e = std::getenv("GE_FAR_R")) item_rows = std::atoi(e) == 4 ? 4 * kFarLeaf : kFarLeaf;
+    pl->far = far_seg_create(st, dim, pl->theta, item_rows, cus, base, size);
   }
   hipLaunchKernelGGL(pos_of_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, pl->pt_ix,
                      pl->pos.p);
@@ -1068,7 +1111,7 @@ static void faml_plan_build(ge_faml_plan* pl, const int* h_pt_ip, const std::vec
                        pl->nrows, pl->rows.p, pl->pt_ip, pl->pt_ix, pl->pos.p, pl->vA, pl->ip,
                        pl->ix, pl->ecode.p);
   }
-  if (pl->nirows > 0)
+  if (pl->nirows > 0 && !dp_done)
     hipLaunchKernelGGL(faml_huge_dp, dim3((pl->nirows + kHT - 1) / kHT), dim3(kHT), 0, st,
                        pl->nirows, pl->irows.p, pl->pt_ix, pl->vA, pl->ip, pl->ix, pl->dx, pl->DP.p,
                        pl->c.use_weights);
@@ -1088,10 +1131,14 @@ template <int D>
 static void faml_launch_repulse(ge_faml_plan* pl, hipStream_t ss, int* queue, const double* cur,
                                 double* F) {
   const FaConst& c = pl->c;
-  if (pl->fast) {
-    if constexpr (D <= kNarrowMaxDim)  // fast is never set on the wide schedule
-      hipLaunchKernelGGL((faml_fast_repulse<D, kFastR>), dim3(pl->fast_blocks), dim3(kHT), 0, ss,
-                         pl->nfitems, pl->fitems.p, queue, pl->pt_ip, cur, pl->DP.p, c.repel, F);
+  if (pl->fast || pl->far) {
+    // the far aggregates' pass first (the largest aggregates), then the FAST items of
+    // the streamed rows that are left; the two write disjoint rows of F
+    if (pl->far) far_seg_repulse(pl->far, ss, cur, pl->DP.p, c.repel, F);
+    if constexpr (D <= kNarrowMaxDim)  // neither is ever set on the wide schedule
+      if (pl->fast)
+        hipLaunchKernelGGL((faml_fast_repulse<D, kFastR>), dim3(pl->fast_blocks), dim3(kHT), 0, ss,
+                           pl->nfitems, pl->fitems.p, queue, pl->pt_ip, cur, pl->DP.p, c.repel, F);
   } else if (pl->sym) {
     if (pl->ntiles) GE_HIP(hipMemsetAsync(pl->prog.p, 0, sizeof(int) * pl->ntiles, ss));
     double* H = pl->hand.p;  // hand-overs component-major (ge_sym.hpp sym_handover)
@@ -1255,6 +1302,7 @@ static void faml_plan_free(ge_faml_plan* pl) {
     if (pl->join[k]) (void)hipEventDestroy(pl->join[k]);
   }
   if (pl->fork) (void)hipEventDestroy(pl->fork);
+  if (pl->far) far_seg_destroy(pl->far);
   delete pl;
 }
 
@@ -1276,7 +1324,9 @@ static void fill_plan(ge_faml_plan* pl, ge_ctx* ctx, ge_comm* comm, int n, const
   pl->pt_ix = d_pt_ix;
   pl->vA = d_vA;
   pl->c = make_fa_const(p);
-  pl->mode = far_as_fast(p).mode;
+  check_far_params(p);
+  pl->mode = p.mode;
+  pl->theta = p.theta;
 }
 
 void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const double* d_dx,
@@ -1416,8 +1466,74 @@ int ge_faml_plan_repulse(ge_faml_plan* pl, const double* d_x, double* d_frep) {
 int ge_faml_plan_mode(ge_faml_plan* pl, int* mode, int* fast_items) {
   return ge::guarded([&] {
     GE_REQUIRE(pl && mode && fast_items, "null argument");
-    *mode = pl->fast ? GE_MODE_FAST : GE_MODE_STRICT;
+    *mode = pl->far ? GE_MODE_FARFIELD : pl->fast ? GE_MODE_FAST : GE_MODE_STRICT;
     *fast_items = pl->nfitems;
+  });
+}
+
+int ge_faml_plan_far_info(ge_faml_plan* pl, int* active, int* reason, double* theta,
+                          int* far_min_ml, int* item_rows, int* key_bits, int* aggregates,
+                          long long* rows, int* bad_boxes, long long* accepted,
+                          long long* exact_leaves, long long* pair_terms, double* prep_ms,
+                          double* item_ms) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl, "null plan");
+    ge::DeviceGuard g(pl->ctx);
+    if (active) *active = pl->far ? 1 : 0;
+    if (reason) *reason = pl->far_reason;
+    if (far_min_ml) *far_min_ml = pl->far_min_ml;
+    if (pl->far) {
+      // the run's passes are on the streamed path's stream, which the context stream
+      // joins at the end of a run; the hook runs on the context stream
+      GE_HIP(hipStreamSynchronize(pl->side[0]));
+      ge::far_seg_info(pl->far, pl->ctx->stream, theta, item_rows, key_bits, aggregates, rows,
+                       bad_boxes, accepted, exact_leaves, pair_terms, prep_ms, item_ms);
+      return;
+    }
+    if (theta) *theta = pl->theta;
+    if (item_rows) *item_rows = 0;
+    if (key_bits) *key_bits = 0;
+    if (aggregates) *aggregates = 0;
+    if (rows) *rows = 0;
+    if (bad_boxes) *bad_boxes = 0;
+    if (accepted)
+      for (int l = 0; l < GE_FAR_MAX_LEVELS; ++l) accepted[l] = 0;
+    if (exact_leaves) *exact_leaves = 0;
+    if (pair_terms) *pair_terms = 0;
+    if (prep_ms) *prep_ms = 0.0;
+    if (item_ms) *item_ms = 0.0;
+  });
+}
+
+int ge_faml_plan_far_aggregates(ge_faml_plan* pl, int* aggs) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && aggs, "null argument");
+    std::copy(pl->faraggs.begin(), pl->faraggs.end(), aggs);
+  });
+}
+
+// the far aggregate's index in the engine, or GE_ERR_ARG
+static int far_segment_of(ge_faml_plan* pl, int agg) {
+  GE_REQUIRE(pl, "null plan");
+  const auto it = std::find(pl->faraggs.begin(), pl->faraggs.end(), agg);
+  GE_REQUIRE(pl->far && it != pl->faraggs.end(), "not a far-field aggregate of this plan");
+  return (int)(it - pl->faraggs.begin());
+}
+
+int ge_faml_plan_far_shape(ge_faml_plan* pl, int agg, int* members, int* levels,
+                           int* level_cells, int* items) {
+  return ge::guarded([&] {
+    ge::far_seg_shape(pl->far, far_segment_of(pl, agg), members, levels, level_cells, items);
+  });
+}
+
+int ge_faml_plan_far_layout(ge_faml_plan* pl, int agg, int* perm, unsigned long long* keys,
+                            double* box, double* cells, double* items) {
+  return ge::guarded([&] {
+    const int f = far_segment_of(pl, agg);
+    ge::DeviceGuard g(pl->ctx);
+    GE_HIP(hipStreamSynchronize(pl->side[0]));
+    ge::far_seg_layout(pl->far, pl->ctx->stream, f, perm, keys, box, cells, items);
   });
 }
 
@@ -1515,8 +1631,7 @@ int ge_faml_sched_create(int m, const int* h_pt_ip, const int* h_aggs, int n_agg
     auto* h = new ge_faml_sched();
     std::unique_ptr<ge_faml_sched> hold(h);
     h->s = ge::faml_schedule(ge::faml_sched_in(h_pt_ip, aggs, split, rank, nranks, dim,
-                                               mode == GE_MODE_FARFIELD ? GE_MODE_FAST : mode, cus,
-                                               sym_occ));
+                                               mode, cus, sym_occ));
     const ge::FamlSched& s = h->s;
     h->scalars = {s.res_cap, s.census[0], s.census[1], s.census[2], s.census[3],
                   (int)s.off_m, (int)s.off_l, s.ns, s.nm, s.nl,
@@ -1546,6 +1661,7 @@ int ge_faml_sched_table(const ge_faml_sched* h, int k, const int** data, long lo
       case GE_FAML_SCHED_FITEMS: put(s.fitems.data(), 4 * s.fitems.size()); break;
       case GE_FAML_SCHED_UNITS: put(s.units.data(), 4 * s.units.size()); break;
       case GE_FAML_SCHED_SCALARS: put(h->scalars.data(), h->scalars.size()); break;
+      case GE_FAML_SCHED_FARAGGS: put(s.faraggs.data(), s.faraggs.size()); break;
       default: throw ge::Error(GE_ERR_ARG, "unknown schedule table");
     }
   });

@@ -32,6 +32,14 @@ constexpr int kBigDefaultR = 1, kBigDefaultU = 1;
 // tiles of one faml_fast_repulse item, waves of one faml_sym_repulse block, and the
 // unit kinds of ge_sym.hpp.
 constexpr int kSchedFastR = 4, kSchedSymWaves = 4, kSchedSweep = 0, kSchedRows = 1;
+// GE_MODE_FARFIELD: the smallest streamed aggregate that takes the far field (ge_far.hip,
+// the segmented engine): the smallest swept size from which FARFIELD's range lay wholly
+// below FAST's on levels of equal aggregates, 4M rows, d = 3, theta = 0.5 (ms per step,
+// FAST / FARFIELD: 2^12 13.21-13.29 / 12.99-13.05, 2^13 25.6 / 18.5-18.7, 2^14 50.5 /
+// 26.7-26.9, 2^15 99.5 / 38.3-38.8, 2^16 197.5 / 51.1-51.5; profiles/r19/crossover.jsonl),
+// and never below 4096.  A streamed aggregate has more than 256 members, so an override
+// is held to 257 at least.
+constexpr int kFarMinMlDefault = 4096;
 
 // The schedule's knobs, from the environment (faml_knobs_from_env).
 struct FamlKnobs {
@@ -40,6 +48,7 @@ struct FamlKnobs {
   int R = kBigDefaultR, U = kBigDefaultU;  // GE_FAML_R / GE_FAML_U
   bool sym = true;                         // GE_FAML_SYM (0: no symmetric sweeps)
   double chain_k = 2.5;                    // GE_FAML_SYM_CHAIN (0: all sweeps)
+  int far_min_ml = kFarMinMlDefault;       // GE_FAR_MIN_ML
 };
 
 inline FamlKnobs faml_knobs_from_env() {
@@ -52,6 +61,7 @@ inline FamlKnobs faml_knobs_from_env() {
   if (const char* e = std::getenv("GE_FAML_U")) k.U = std::atoi(e);
   if (const char* e = std::getenv("GE_FAML_SYM")) k.sym = *e != '0';
   if (const char* e = std::getenv("GE_FAML_SYM_CHAIN")) k.chain_k = std::atof(e);  // 0: all sweeps
+  if (const char* e = std::getenv("GE_FAR_MIN_ML")) k.far_min_ml = std::max(257, std::atoi(e));
   return k;
 }
 
@@ -81,6 +91,7 @@ struct FamlSched {
   int R = kBigDefaultR, U = kBigDefaultU, code = 0;
   std::vector<SchedInt2> items;   // STRICT (aggregate, first row), descending work
   std::vector<SchedInt4> fitems;  // FAST (aggregate, first row, end row, 0), descending work
+  std::vector<int> faraggs;       // FARFIELD: the whole streamed aggregates on the far field, larger first
   bool fast = false, sym = false, wide = false;
   std::vector<SchedInt4> units;  // (aggregate, row tile, progress offset or priority, kind)
   int ntiles = 0, swept = 0, rows_mode = 0, sym_blocks = 0;
@@ -253,12 +264,17 @@ inline void strict_items(const Work& w, FamlSched& s) {
   s.code = big_code(R, U);
 }
 
-// FAST mode: row items of up to kSchedFastR 64-row tiles, whole aggregates and this rank's
+// FAST mode, and FARFIELD mode for the aggregates that do not take the far field: row
+// items of up to kSchedFastR 64-row tiles, whole aggregates and this rank's
 // tiles of the split ones alike (a row's sum does not depend on the item it is in);
 // the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) do not apply
 inline void fast_items(const Work& w, FamlSched& s) {
   const FamlSchedIn& in = w.in;
-  if (in.mode == GE_MODE_FAST && !in.wide) {
+  const bool far = in.mode == GE_MODE_FARFIELD && !in.wide && in.dim <= 4;
+  if (far)  // the size-qualified whole aggregates (w.big: larger first); the rest are FAST items
+    for (int a : w.big)
+      if (w.size_of(a) >= in.knobs.far_min_ml) s.faraggs.push_back(a);
+  if ((in.mode == GE_MODE_FAST || in.mode == GE_MODE_FARFIELD) && !in.wide) {
     struct FItem { int a, r0, r1; double work; };
     std::vector<FItem> fi;
     auto cut = [&](int a, int b0, int b1) {  // rows [b0, b1) of aggregate a
@@ -268,7 +284,8 @@ inline void fast_items(const Work& w, FamlSched& s) {
         fi.push_back({a, r0, r1, (double)((r1 - r0 + 63) / 64) * sz});
       }
     };
-    for (int a : w.big) cut(a, 0, w.size_of(a));
+    for (int a : w.big)
+      if (!far || w.size_of(a) < in.knobs.far_min_ml) cut(a, 0, w.size_of(a));
     for (int a : *in.split) {
       const Tiles t = w.tiles_of(a, in.rank);
       cut(a, 64 * t.t0, w.row_end(a, t));
@@ -419,7 +436,7 @@ inline FamlSched faml_schedule(const FamlSchedIn& in) {
   sched::owned_rows(w, s);
   sched::strict_items(w, s);
   sched::fast_items(w, s);
-  s.sym = in.knobs.sym && !in.wide && !s.fast;
+  s.sym = in.knobs.sym && !in.wide && !s.fast && s.faraggs.empty();
   if (s.sym && !s.huge.empty()) {
     std::vector<int> T(w.big.size());
     for (size_t b = 0; b < w.big.size(); ++b) T[b] = w.ntiles_of(w.big[b]);

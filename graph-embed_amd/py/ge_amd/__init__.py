@@ -144,6 +144,16 @@ _SIGS = {
     "ge_faml_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ge_faml_plan_mode": (ctypes.c_int, [_vp, _ip, _ip]),
     "ge_faml_plan_repulse": (ctypes.c_int, [_vp, _vp, _vp]),
+    "ge_faml_plan_far_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_double), _ip,
+                                             _ip, _ip, _ip, ctypes.POINTER(ctypes.c_longlong), _ip,
+                                             ctypes.POINTER(ctypes.c_longlong),
+                                             ctypes.POINTER(ctypes.c_longlong),
+                                             ctypes.POINTER(ctypes.c_longlong),
+                                             ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double)]),
+    "ge_faml_plan_far_aggregates": (ctypes.c_int, [_vp, _vp]),
+    "ge_faml_plan_far_shape": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip, _ip, _ip]),
+    "ge_faml_plan_far_layout": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "ge_faml_plan_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ge_faml_plan_kernel_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double), _ip]),
@@ -627,6 +637,7 @@ def row_shard(n, nranks, rank):
 
 FAML_SCHED_TABLES = ("order", "beg", "rows", "irows", "huge", "xrows", "xcounts", "items",
                      "fitems", "units")  # GE_FAML_SCHED_*; the scalars follow
+FAML_SCHED_FARAGGS = 11  # GE_FAML_SCHED_FARAGGS: faml_schedule()["faraggs"]
 FAML_SCHED_SCALARS = ("res_cap", "small", "mid", "large", "streamed", "off_mid", "off_large",
                       "blocks_small", "blocks_mid", "blocks_large", "R", "U", "code", "fast",
                       "sym", "wide", "ntiles", "sweeps", "row_blocks", "sym_blocks")
@@ -636,8 +647,9 @@ def faml_schedule(pt_indptr, dim, cus, sym_occ, aggs=None, split=None, rank=0, n
                   mode=MODE_STRICT):
     """The schedule a FamlPlan over these aggregates would settle on, without a device
     (ge_faml_sched_*): {table name: int32 array} for FAML_SCHED_TABLES, the scalars of
-    FAML_SCHED_SCALARS and streamed_pairs.  aggs: default all; the GE_FAML_* knobs
-    are read from the environment as the plan reads them."""
+    FAML_SCHED_SCALARS, streamed_pairs and faraggs (mode=MODE_FARFIELD: the aggregates
+    that take the far field, larger first).  aggs: default all; the GE_FAML_* knobs and
+    GE_FAR_MIN_ML are read from the environment as the plan reads them."""
     pip = np.ascontiguousarray(pt_indptr, dtype=np.int32)
     m = len(pip) - 1
     ids = np.ascontiguousarray(np.arange(m) if aggs is None else aggs, dtype=np.int32)
@@ -653,6 +665,10 @@ def faml_schedule(pt_indptr, dim, cus, sym_occ, aggs=None, split=None, rank=0, n
             out[name] = (np.ctypeslib.as_array(p, (n.value,)).astype(np.int32) if n.value
                          else np.zeros(0, dtype=np.int32))
         out.update(zip(FAML_SCHED_SCALARS, (int(v) for v in out.pop("scalars"))))
+        p, n = _ip(), ctypes.c_longlong()
+        _check(lib().ge_faml_sched_table(h, FAML_SCHED_FARAGGS, ctypes.byref(p), ctypes.byref(n)))
+        out["faraggs"] = (np.ctypeslib.as_array(p, (n.value,)).astype(np.int32) if n.value
+                          else np.zeros(0, dtype=np.int32))
         d = ctypes.c_double()
         _check(lib().ge_faml_sched_pairs(h, ctypes.byref(d)))
         out["streamed_pairs"] = d.value
@@ -695,14 +711,16 @@ class FamlPlan:
                                              ctypes.byref(p), iterations, a0, a1,
                                              ctypes.byref(h)))
         self.h = h
+        self.dim = dim
 
     def run(self, d_cA, d_rA, d_init, d_x):
         _check(lib().ge_faml_plan_run(self.h, _vp(d_cA), _vp(d_rA), _vp(d_init), _vp(d_x)))
 
     def mode(self):
-        """(mode, fast_items): MODE_FAST only when the closed-form repulsion kernel is
-        scheduled for the streamed aggregates, with its row items per launch
-        (ge_faml_plan_mode); otherwise (MODE_STRICT, 0)."""
+        """(mode, fast_items): MODE_FARFIELD when an aggregate runs the far field, else
+        MODE_FAST only when the closed-form repulsion kernel is scheduled for the streamed
+        aggregates; fast_items: its row items per launch (ge_faml_plan_mode); otherwise
+        (MODE_STRICT, 0)."""
         a, b = ctypes.c_int(), ctypes.c_int()
         _check(lib().ge_faml_plan_mode(self.h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
@@ -712,6 +730,54 @@ class FamlPlan:
         P_T storage order) into d_frep, same layout; other members' positions are left
         untouched (ge_faml_plan_repulse)."""
         _check(lib().ge_faml_plan_repulse(self.h, _vp(d_x), _vp(d_frep)))
+
+    def far_info(self):
+        """ge_faml_plan_far_info: active, reason (FAR_REASONS), theta, far_min_ml, item_rows,
+        key_bits (per axis), aggregates (the far aggregates' ids, larger first), rows and, of
+        the last pass, bad_boxes, accepted (cells per level, GE_FAR_MAX_LEVELS entries),
+        exact_leaves, pair_terms, prep_ms, item_ms."""
+        act, why, fmin, rows_i, bits, nagg, bad = (ctypes.c_int() for _ in range(7))
+        th, prep, item = (ctypes.c_double() for _ in range(3))
+        acc = (ctypes.c_longlong * FAR_MAX_LEVELS)()
+        rows, leaves, terms = (ctypes.c_longlong() for _ in range(3))
+        _check(lib().ge_faml_plan_far_info(
+            self.h, ctypes.byref(act), ctypes.byref(why), ctypes.byref(th), ctypes.byref(fmin),
+            ctypes.byref(rows_i), ctypes.byref(bits), ctypes.byref(nagg), ctypes.byref(rows),
+            ctypes.byref(bad), acc, ctypes.byref(leaves), ctypes.byref(terms), ctypes.byref(prep),
+            ctypes.byref(item)))
+        aggs = np.zeros(nagg.value, dtype=np.int32)
+        if nagg.value:
+            _check(lib().ge_faml_plan_far_aggregates(self.h, aggs.ctypes.data_as(_vp)))
+        return {"active": bool(act.value), "reason": FAR_REASONS[why.value], "theta": th.value,
+                "far_min_ml": fmin.value, "item_rows": rows_i.value, "key_bits": bits.value,
+                "aggregates": [int(a) for a in aggs], "rows": rows.value,
+                "bad_boxes": bad.value, "accepted": list(acc), "exact_leaves": leaves.value,
+                "pair_terms": terms.value, "prep_ms": prep.value, "item_ms": item.value}
+
+    def far_layout(self, agg):
+        """ge_faml_plan_far_layout: what the last pass used for far aggregate `agg`, in the
+        form of FaPlan.far_layout(): perm (the position within the aggregate at each sorted
+        position), keys, box, cells (one array per level, leaves first), items, item_rows,
+        theta and key_bits."""
+        info = self.far_info()
+        mem, lv, nit = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        cnt = (ctypes.c_int * FAR_MAX_LEVELS)()
+        _check(lib().ge_faml_plan_far_shape(self.h, agg, ctypes.byref(mem), ctypes.byref(lv), cnt,
+                                            ctypes.byref(nit)))
+        s, d, L = mem.value, self.dim, lv.value
+        level_cells = list(cnt)[:L]
+        perm = np.empty(s, dtype=np.int32)
+        keys = np.empty(s, dtype=np.uint64)
+        box = np.empty(d + 1)
+        cells = np.empty((sum(level_cells), d + 2))
+        items = np.empty((nit.value, d + 2))
+        _check(lib().ge_faml_plan_far_layout(self.h, agg, *(a.ctypes.data_as(_vp)
+                                                            for a in (perm, keys, box, cells, items))))
+        offs = np.cumsum([0] + level_cells)
+        return {"perm": perm, "keys": keys, "box": box, "items": items,
+                "item_rows": info["item_rows"], "theta": info["theta"],
+                "key_bits": info["key_bits"],
+                "cells": [cells[offs[l]:offs[l + 1]] for l in range(L)]}
 
     def set_profiling(self, on):
         _check(lib().ge_faml_plan_set_profiling(self.h, int(on)))

@@ -82,10 +82,35 @@ extern "C" {
  * measured crossover against FAST at dim 3; GE_FAR_MIN overrides).  In every other case -- row shards and ge_force_atlas_dist,
  * dim >= 5, a non-positive mass, a small level -- and in an iteration whose bounding
  * box is not finite, the plan runs exactly what GE_MODE_FAST runs, with the same bits.
- * ge_faml_plan_*, ge_force_atlas_ml, ge_embed and their *_dist forms treat it as
- * GE_MODE_FAST.  theta is ge_fa_params.theta, 0 <= theta < 1.  An iteration of this
+ * theta is ge_fa_params.theta, 0 <= theta < 1.  A single-level iteration of this
  * mode synchronises the stream once (the box check), so its steps cannot be captured
- * into a graph; ge_force_atlas does not capture them. */
+ * into a graph; ge_force_atlas does not capture them.
+ *
+ * The multilevel level (ge_faml_plan_create, _create_subset, _create_shard, and through
+ * them ge_force_atlas_ml, ge_embed, the *_dist forms and the drop-in headers) honours
+ * the mode per streamed aggregate.  A streamed aggregate takes the far field when
+ * dim <= 4 (not the wide schedule), it has at least far_min_ml members (4096, the measured crossover against FAST at dim 3;
+ * GE_FAR_MIN_ML overrides, held to 257 at least), the plan holds it whole (not one of a
+ * shard plan's split aggregates) and every internal deg + 1 of the plan's streamed rows
+ * is finite and > 0 (checked once at plan creation; a failure sends the whole plan to
+ * FAST, reason GE_FAR_MASS).  Everything else -- every other streamed aggregate, all
+ * resident aggregates, member rows, init, centring and radius steps -- runs exactly as
+ * under GE_MODE_FAST, with FAST's bits; a plan without a far aggregate is a FAST plan.
+ * Per far aggregate and iteration the scheme above is applied to its members alone:
+ * its own box and scale, Morton keys of GE_FAR_ML_KEY_BITS(dim) bits per axis (41 / 20 /
+ * 13 / 10 at dim 1 / 2 / 3 / 4: the aggregate's rank in the plan shares the one sort's
+ * key), members ordered by (key, position in P_T storage order), leaves of 64, 16 cells
+ * per parent up to a top of at most 16 cells, items of item_rows consecutive sorted
+ * rows of one aggregate.  A walk never leaves its aggregate, and the bound above holds
+ * per row with the internal degree and the sum of include/forceatlas.hpp:394-410 over
+ * the aggregate's members.  ge_faml_plan_run synchronises nowhere: an aggregate whose
+ * coordinates are not all finite in an iteration gets all-zero keys (P_T order) and a
+ * device flag that rejects every cell, so its rows are one lane's chain over its
+ * members in P_T order, GE_MODE_FAST's bits; an aggregate whose members coincide needs
+ * nothing special (the 1e-5 gap rejects every cell).  Results are deterministic and the
+ * same for whole and subset plans.  A shard plan's split aggregates get FAST's bits, so
+ * a split aggregate differs from the same aggregate in a whole plan; sharding one
+ * aggregate's far field over ranks is not offered. */
 #define GE_MODE_FARFIELD 2
 
 typedef struct ge_ctx ge_ctx;
@@ -221,7 +246,8 @@ int ge_fa_plan_rows_info(ge_fa_plan* plan, int* classes, int* heavy_rows, int* h
 #define GE_FAR_DIM 2           /* dim >= 5 or the wide schedule */
 #define GE_FAR_ROW_SHARD 3     /* the plan does not hold every row */
 #define GE_FAR_MASS 4          /* some deg + 1 is not > 0 */
-#define GE_FAR_SMALL 5         /* n < far_min */
+#define GE_FAR_SMALL 5         /* n < far_min; multilevel: no streamed aggregate reaches far_min_ml */
+#define GE_FAR_ML_KEY_BITS(dim) (41 / (dim)) /* multilevel Morton bits per axis, dim 1..4 */
 int ge_fa_plan_far_info(ge_fa_plan* plan, int* active, int* reason, double* theta,
                         int* item_rows, int* levels, int* level_cells, long long* level_points,
                         int* fallback, long long* accepted, long long* exact_leaves,
@@ -284,10 +310,12 @@ int ge_faml_plan_create_shard(ge_ctx* ctx, ge_comm* comm, int n, const int* d_in
                               int n_aggs, const int* h_split, int n_split, ge_faml_plan** out);
 int ge_faml_plan_run(ge_faml_plan* plan, const double* d_coords_A, const double* d_r_A,
                      const double* d_init, double* d_coords);
-/* The mode the plan runs: GE_MODE_FAST only when faml_fast_repulse is scheduled (the
- * caller asked for it, the plan has streamed rows and dim is not on the wide
- * schedule), with the row items of one launch; otherwise GE_MODE_STRICT and 0.  Under
- * FAST the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) are ignored and
+/* The mode the plan runs: GE_MODE_FARFIELD when at least one aggregate runs the far
+ * field; else GE_MODE_FAST only when faml_fast_repulse is scheduled (the caller asked
+ * for FAST or FARFIELD, the plan has streamed rows and dim is not on the wide
+ * schedule); otherwise GE_MODE_STRICT.  fast_items: the row items of one
+ * faml_fast_repulse launch (under FARFIELD: those that remain).  Under FAST and
+ * FARFIELD the STRICT schedule knobs (GE_FAML_SYM*, GE_FAML_R / U) are ignored and
  * ge_faml_plan_schedule reports zeros. */
 int ge_faml_plan_mode(ge_faml_plan* plan, int* mode, int* fast_items);
 /* One repulsion pass of the plan's streamed aggregates alone (include/forceatlas.hpp:
@@ -297,12 +325,39 @@ int ge_faml_plan_mode(ge_faml_plan* plan, int* mode, int* fast_items);
  * mode.  A measurement and test hook like ge_fa_plan_attract; it synchronises and
  * does not disturb later runs. */
 int ge_faml_plan_repulse(ge_faml_plan* plan, const double* d_x, double* d_frep);
+/* GE_MODE_FARFIELD diagnostics of a multilevel plan.  active: at least one aggregate
+ * runs the far field; reason: why not (GE_FAR_*).  theta, far_min_ml, rows per item,
+ * Morton key bits per axis, the far aggregates and their rows.  Of the last pass
+ * (ge_faml_plan_repulse, or the last iteration of a run): the aggregates whose box was
+ * not finite, cells accepted per level (GE_FAR_MAX_LEVELS), leaves evaluated pair by
+ * pair, pair terms, and the device ms of the pass before the item kernel and of the
+ * item kernel.  Any output pointer may be NULL.  Synchronises; results do not depend
+ * on it. */
+int ge_faml_plan_far_info(ge_faml_plan* plan, int* active, int* reason, double* theta,
+                          int* far_min_ml, int* item_rows, int* key_bits, int* aggregates,
+                          long long* rows, int* bad_boxes, long long* accepted,
+                          long long* exact_leaves, long long* pair_terms, double* prep_ms,
+                          double* item_ms);
+/* The plan's far aggregates (ge_faml_plan_far_info's count), larger first, and the
+ * sizes of one's layout: members, levels, cells per level from the leaves up
+ * (GE_FAR_MAX_LEVELS ints) and items.  GE_ERR_ARG if agg is not a far aggregate. */
+int ge_faml_plan_far_aggregates(ge_faml_plan* plan, int* aggs);
+int ge_faml_plan_far_shape(ge_faml_plan* plan, int agg, int* members, int* levels,
+                           int* level_cells, int* items);
+/* What the last pass used for far aggregate agg, in ge_fa_plan_far_layout's record
+ * form: perm (the position within the aggregate at each sorted position), keys (the
+ * sorted Morton keys), box (dim + 1), cells per level from the leaves up and items.
+ * GE_ERR_ARG if agg is not a far aggregate of the plan, GE_ERR_STATE before a pass.
+ * Any pointer may be NULL.  Synchronises. */
+int ge_faml_plan_far_layout(ge_faml_plan* plan, int agg, int* perm, unsigned long long* keys,
+                            double* box, double* cells, double* items);
 int ge_faml_plan_set_profiling(ge_faml_plan* plan, int enable);
-/* Average device ms of the resident (LDS) kernels and of the streamed path per run. */
+/* Average device ms of the resident (LDS) kernels and of the streamed path per run
+ * (under GE_MODE_FARFIELD the far passes are part of the streamed path). */
 int ge_faml_plan_kernel_ms(ge_faml_plan* plan, double* resident_ms, double* streamed_ms,
                            int* runs);
 /* Average device ms of one streamed-path repulsion launch (the sweeps, faml_big_repulse
- * or, under GE_MODE_FAST, faml_fast_repulse; one per iteration) over the profiled runs, and the ordered pairs one launch
+ * or, under GE_MODE_FAST, faml_fast_repulse, under GE_MODE_FARFIELD the far pass and it; one per iteration) over the profiled runs, and the ordered pairs one launch
  * evaluates (sum of s(s-1) over the streamed aggregates); 0 launches if none. */
 int ge_faml_plan_repulse_ms(ge_faml_plan* plan, double* ms_per_launch, int* launches,
                             double* pairs_per_launch);
@@ -354,6 +409,9 @@ typedef struct ge_faml_sched ge_faml_sched;
 #define GE_FAML_SCHED_FITEMS 8
 #define GE_FAML_SCHED_UNITS 9
 #define GE_FAML_SCHED_SCALARS 10
+/* mode = GE_MODE_FARFIELD: the aggregates that take the far field, larger first (they
+ * are then no FAST items); GE_FAR_MIN_ML is read from the environment like GE_FAML_*. */
+#define GE_FAML_SCHED_FARAGGS 11
 int ge_faml_sched_create(int m, const int* h_pt_indptr, const int* h_aggs, int n_aggs,
                          const int* h_split, int n_split, int rank, int nranks, int dim,
                          int mode, int cus, int sym_occ, ge_faml_sched** out);
