@@ -508,6 +508,47 @@ int ge_force_atlas_dist(ge_comm* c, int n, const int* ip, const int* ix, const d
   });
 }
 
+// Row shards as ge_force_atlas_dist; the shards' rows are gathered once and every rank
+// reduces all n of them with the one-GPU call's kernel.
+int ge_layout_energy_dist(ge_comm* c, int n, const int* ip, const int* ix, const double* dx,
+                          int dim, const double* coords, const ge_fa_params* p, double* rows,
+                          double* totals) {
+  return guarded([&] {
+    ge::check_comm(c);
+    GE_REQUIRE(p, "null argument");
+    GE_REQUIRE(coords && totals, "null coordinates or totals");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
+    GE_REQUIRE(n > 0, "the layout energy needs at least one vertex");
+    ge::check_csr(n, ip, ix, dx);
+    ge::DeviceGuard g(c->ctx);
+    const int N = c->nranks;
+    const int chunk = (n + N - 1) / N;
+    const int rb = std::min(n, c->rank * chunk), re = std::min(n, (c->rank + 1) * chunk);
+    hipStream_t s = c->ctx->stream;
+    ge::DevCsr A(n, ip, ix, dx, s);
+    ge::DevBuf<double> x((size_t)n * dim), out((size_t)N * chunk * GE_ENERGY_COLS);
+    x.upload(coords, (size_t)n * dim, s);
+    ge_fa_params q = *p;
+    q.mode = GE_MODE_FAST;  // the values ignore the mode
+    ge_fa_plan* plan = nullptr;
+    ge::abi(ge_fa_plan_create(c->ctx, n, A.nnz, A.ip.p, A.ix.p, A.dx.p, dim, &q, rb, re, &plan));
+    try {
+      // A short or empty last shard (rb == re writes nothing) leaves the tail of its
+      // block as allocated; the blocks are gathered whole, and only the first n rows,
+      // all of them some rank's own, are downloaded or summed.
+      double* mine = out.p + (size_t)c->rank * chunk * GE_ENERGY_COLS;
+      ge::plan_energy_rows(plan, x.p, mine);
+      ge::allgather_dev(c, mine, out.p, sizeof(double) * (size_t)chunk * GE_ENERGY_COLS);
+      if (rows) out.download(rows, (size_t)n * GE_ENERGY_COLS, s);
+      ge::plan_energy_totals(plan, n, out.p, totals);
+    } catch (...) {
+      ge_fa_plan_destroy(plan);
+      throw;
+    }
+    ge::abi(ge_fa_plan_destroy(plan));
+  });
+}
+
 int ge_force_atlas_ml_dist(ge_comm* c, int n, const int* ip, const int* ix, const double* dx,
                            int m, const int* pip, const int* pix, const int* vA,
                            const double* cA, const double* rA, double* coords, int dim,

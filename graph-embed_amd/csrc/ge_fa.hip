@@ -44,6 +44,7 @@
 #include <memory>
 #include <vector>
 
+#include "ge_energy.hpp"
 #include "ge_far.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
@@ -1724,6 +1725,8 @@ struct ge_fa_plan {
   // GE_MODE_FARFIELD (ge_far.hip): the engine when the far field runs, else why not
   ge::FarEngine* far = nullptr;
   int far_reason = GE_FAR_NOT_REQUESTED;
+  // ge_fa_plan_energy's buffers, made by its first call (ge_energy.hpp)
+  std::unique_ptr<ge::EnergyScratch> energy;
   ~ge_fa_plan() {
     ge::far_destroy(far);
     if (sym_err_h) (void)hipHostFree(sym_err_h);
@@ -2152,9 +2155,62 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
   sym_check(&pl);
 }
 
+// The energy columns of the plan's rows on its stream (d_rows == nullptr: into the
+// plan's own buffer); reads the graph, deg + 1 and d_x and writes only the energy scratch,
+// so steps before and after see the plan as it was.
+double* plan_energy_rows(ge_fa_plan* pl, const double* d_x, double* d_rows) {
+  if (!pl->energy) pl->energy = std::make_unique<EnergyScratch>();
+  return energy_rows(pl->ctx->stream, *pl->energy, pl->n, pl->dim, pl->rb, pl->re, pl->ip, pl->ix,
+                     pl->dx, pl->dp1.p, pl->p, d_x, d_rows);
+}
+
+void plan_energy_totals(ge_fa_plan* pl, int rows, const double* d_rows, double* totals) {
+  if (!pl->energy) pl->energy = std::make_unique<EnergyScratch>();
+  energy_totals(pl->ctx->stream, *pl->energy, rows, d_rows, totals);
+}
+
 }  // namespace ge
 
 extern "C" {
+
+int ge_fa_plan_energy(ge_fa_plan* pl, const double* d_x, double* d_rows, double* totals) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && d_x && totals, "bad plan energy arguments (null plan, coordinates or totals)");
+    ge::DeviceGuard g(pl->ctx);
+    const double* rows = ge::plan_energy_rows(pl, d_x, d_rows);
+    ge::plan_energy_totals(pl, pl->re - pl->rb, rows, totals);
+  });
+}
+
+int ge_layout_energy(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx, int dim,
+                     const double* coords, const ge_fa_params* p, double* rows, double* totals) {
+  return ge::guarded([&] {
+    GE_REQUIRE(ctx && p, "null argument");
+    GE_REQUIRE(coords && totals, "null coordinates or totals");
+    GE_REQUIRE(dim >= 1 && dim <= ge::kMaxDim, "dimension must be 1..16");
+    GE_REQUIRE(n > 0, "the layout energy needs at least one vertex");
+    ge::check_csr(n, ip, ix, dx);
+    ge::DeviceGuard g(ctx);
+    hipStream_t s = ctx->stream;
+    ge::DevCsr A(n, ip, ix, dx, s);
+    ge::DevBuf<double> x((size_t)n * dim), out((size_t)n * GE_ENERGY_COLS);
+    x.upload(coords, (size_t)n * dim, s);
+    ge_fa_params q = *p;
+    q.mode = GE_MODE_FAST;  // the values ignore the mode; a FAST plan builds no sweep tables
+    ge_fa_plan* plan = nullptr;
+    if (int rc = ge_fa_plan_create(ctx, n, A.nnz, A.ip.p, A.ix.p, A.dx.p, dim, &q, 0, n, &plan))
+      throw ge::Error(rc, ge_last_error());
+    try {
+      ge::plan_energy_rows(plan, x.p, out.p);
+      if (rows) out.download(rows, (size_t)n * GE_ENERGY_COLS, s);
+      ge::plan_energy_totals(plan, n, out.p, totals);
+    } catch (...) {
+      ge_fa_plan_destroy(plan);
+      throw;
+    }
+    if (int rc = ge_fa_plan_destroy(plan)) throw ge::Error(rc, ge_last_error());
+  });
+}
 
 int ge_fa_plan_create(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix,
                       const double* d_dx, int dim, const ge_fa_params* p, int rb, int re,

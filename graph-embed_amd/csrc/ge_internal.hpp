@@ -251,6 +251,12 @@ int sym_blocks_per_cu(int dim);
 void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix,
                    const double* d_dx, int dim, double* d_x, int iterations,
                    const ge_fa_params& p);
+// The layout energy on a plan (ge_fa.hip over ge_energy.hip): the five columns of the
+// plan's rows into d_rows (device; nullptr: the plan's own buffer, returned) on its
+// stream, and the column sums of `rows` rows of d_rows into totals (host, 5;
+// synchronises).  Both touch only the plan's energy scratch.
+double* plan_energy_rows(ge_fa_plan* pl, const double* d_x, double* d_rows);
+void plan_energy_totals(ge_fa_plan* pl, int rows, const double* d_rows, double* totals);
 void faml_run_device(ge_ctx* ctx, int n, const int* d_ip, const int* d_ix, const double* d_dx,
                      int m, const int* h_pt_ip, const int* d_pt_ip, const int* d_pt_ix,
                      const int* d_vA, const double* d_cA, const double* d_rA,

@@ -13,6 +13,7 @@
 #ifndef FORCEATLAS_HPP
 #define FORCEATLAS_HPP
 
+#include <array>
 #include <cassert>
 #include <cmath>
 #include <vector>
@@ -111,6 +112,33 @@ inline void forceAtlasMultilevel(const SparseMatrix& A, const SparseMatrix& P,
                                   P.GetIndptr().data(), P.GetIndices().data(), v_A.data(),
                                   cA.data(), r_A.data(), X.data(), dim, iterations, &p));
   detail::unflatten(X, n, dim, coords);
+}
+
+// An addition: the reference has no such function.  The layout energy of include/ge.h
+// ("layout energy") of the coordinates on graph A: the totals {REP, ATT, GRAV, PAIRDIST,
+// EDGELEN} (GE_ENERGY_*), E = [0] + [1] + [2]; -dE/dx is forceAtlas's force for a
+// symmetric A with nohubs = false.  Parameters and defaults are forceAtlas's.
+inline std::array<double, GE_ENERGY_COLS> layoutEnergy(
+    const SparseMatrix& A, const std::vector<std::vector<double>>& coords, const double repel = 1.0,
+    const double attract = 1.0, const double gravity = 1.0, const bool useWeights = true,
+    const bool linlog = false, const bool nohubs = false, const double delta = 1.0) {
+  ge_fa_params p;
+  ge_fa_params_default(&p);
+  p.repel = repel;
+  p.attract = attract;
+  p.gravity = gravity;
+  p.use_weights = useWeights;
+  p.linlog = linlog;
+  p.nohubs = nohubs;
+  p.delta = delta;
+  const int n = A.Rows();
+  const int dim = coords.empty() ? 0 : (int)coords[0].size();
+  std::vector<double> X = detail::flatten(coords, n, dim);
+  std::array<double, GE_ENERGY_COLS> totals{};
+  detail::check(ge_layout_energy(detail::context(), n, A.GetIndptr().data(),
+                                 A.GetIndices().data(), A.GetData().data(), dim, X.data(), &p,
+                                 nullptr, totals.data()));
+  return totals;
 }
 
 }  // namespace partition

@@ -32,6 +32,9 @@ MODE_STRICT = 0
 MODE_FAST = 1
 MODE_FARFIELD = 2
 FAR_MAX_LEVELS = 8  # GE_FAR_MAX_LEVELS
+# the columns of the layout energy (GE_ENERGY_*, include/ge.h)
+ENERGY_COLS = 5
+ENERGY_REP, ENERGY_ATT, ENERGY_GRAV, ENERGY_PAIRDIST, ENERGY_EDGELEN = range(ENERGY_COLS)
 # ge_fa_plan_far_info reason codes (GE_FAR_*)
 FAR_REASONS = ("active", "not_requested", "dim", "row_shard", "mass", "small")
 # GE_ROW_*: how the last row pass finished a heavy row (FaPlan.rows_info)
@@ -75,6 +78,9 @@ _SIGS = {
     "ge_fa_plan_attract": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "ge_fa_plan_repulse": (ctypes.c_int, [_vp, _vp, _vp]),
     "ge_fa_plan_forces": (ctypes.c_int, [_vp, _vp]),
+    "ge_fa_plan_energy": (ctypes.c_int, [_vp, _vp, _vp, _f64p]),
+    "ge_layout_energy": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
+                                        _f64p, ctypes.POINTER(FaParams), _vp, _f64p]),
     "ge_fa_plan_rows_info": (ctypes.c_int, [_vp, _ip, _vp, _vp]),
     "ge_fa_plan_far_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_double), _ip, _ip,
                                            _ip, ctypes.POINTER(ctypes.c_longlong), _ip,
@@ -213,6 +219,8 @@ _SIGS = {
     "ge_force_atlas_dist": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
                                            _f64p, ctypes.c_int, ctypes.c_int,
                                            ctypes.POINTER(FaParams)]),
+    "ge_layout_energy_dist": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
+                                             _f64p, ctypes.POINTER(FaParams), _vp, _f64p]),
     "ge_force_atlas_ml_dist": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p,
                                               ctypes.c_int, _i32p, _i32p, _i32p, _f64p, _f64p,
                                               _f64p, ctypes.c_int, ctypes.c_int,
@@ -285,6 +293,26 @@ def _csr(A):
     ip, ix, dx = A
     return (np.ascontiguousarray(ip, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.int32),
             np.ascontiguousarray(dx, dtype=np.float64))
+
+
+def _layout_energy(fn, handle, A, X, rows, kw):
+    ip, ix, dx = _csr(A)
+    n = len(ip) - 1
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"coordinates must be n x dim with n = {n}, got {X.shape}")
+    out = np.empty((n, ENERGY_COLS)) if rows else None
+    totals = np.empty(ENERGY_COLS)
+    p = params(**kw)
+    _check(fn(handle, n, ip, ix, dx, X.shape[1], X.reshape(-1), ctypes.byref(p),
+              out.ctypes.data if rows else None, totals))
+    return out, totals
+
+
+def relative_edge_length(totals, n, nnz):
+    """lambda of include/ge.h: the mean length of a stored entry over the mean distance
+    of a pair; scale-free, 1 for a random layout."""
+    return (totals[ENERGY_EDGELEN] / nnz) / (totals[ENERGY_PAIRDIST] / (n * (n - 1.0)))
 
 
 class Context:
@@ -467,6 +495,12 @@ class Context:
                                    out.reshape(-1)))
         return out
 
+    def layout_energy(self, A, X, rows=True, **kw):
+        """(rows, totals) of the layout X (n x dim) of graph A: the five ENERGY_* columns per
+        vertex (n x 5; None with rows=False) and their sums (ge_layout_energy).  E is
+        totals[ENERGY_REP] + totals[ENERGY_ATT] + totals[ENERGY_GRAV]."""
+        return _layout_energy(lib().ge_layout_energy, self.h, A, X, rows, kw)
+
     def fa_plan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw):
         return FaPlan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw)
 
@@ -566,6 +600,11 @@ class Comm:
         _check(lib().ge_force_atlas_dist(self.h, n, ip, ix, dx, dim, X.reshape(-1),
                                          int(coords is None), iterations, ctypes.byref(p)))
         return X
+
+    def layout_energy(self, A, X, rows=True, **kw):
+        """Context.layout_energy over row shards (ge_layout_energy_dist): the same bits on
+        every rank."""
+        return _layout_energy(lib().ge_layout_energy_dist, self.h, A, X, rows, kw)
 
     def force_atlas_ml(self, A, PT, vertex_A, coords_A, r_A, dim, iterations=10, **kw):
         ip, ix, dx = _csr(A)
@@ -871,6 +910,14 @@ class FaPlan:
         """Copies the forces of the last step or attract ((row_end - row_begin) * dim
         doubles) to the device buffer d_out on the plan's stream (ge_fa_plan_forces)."""
         _check(lib().ge_fa_plan_forces(self.h, _vp(d_out)))
+
+    def energy(self, d_x, d_rows=None):
+        """The totals (5 doubles, ENERGY_*) of the layout energy of the coordinates d_x
+        (n * dim, device) over the plan's rows; d_rows (device, rows * 5) receives the
+        per-row columns (ge_fa_plan_energy).  Synchronises; the plan is not disturbed."""
+        totals = np.empty(ENERGY_COLS)
+        _check(lib().ge_fa_plan_energy(self.h, _vp(d_x), _vp(d_rows) if d_rows else None, totals))
+        return totals
 
     def rows_info(self):
         """ge_fa_plan_rows_info: ntiles, nheavy, nmed, nlight, nseg, seg_mode of the plan's

@@ -263,6 +263,64 @@ int ge_fa_plan_far_layout(ge_fa_plan* plan, int* perm, unsigned long long* keys,
                           double* cells, double* items);
 int ge_fa_plan_destroy(ge_fa_plan* plan);
 
+/* ---- layout energy ----
+ * A yardstick for a layout, whatever produced it (graph-embed_amd/csrc/ge_energy.hip;
+ * the reference has no such function).  With m_i = deg_i + 1 as the iteration uses it (the
+ * weighted row sum under use_weights, else the entry count), d_ij = |x_i - x_j|_2,
+ * dh_ij = max(d_ij, 1e-5) (the reference's clamp), a'_ik the attraction weight of a stored
+ * entry as include/forceatlas.hpp:180-191 forms it (a = 1 without use_weights; a' = a at
+ * delta == 1, 1 at delta == 0, sign(a) |a|^delta otherwise) and psi(d) = d^2 / 2, or
+ * (1 + d) log(1 + d) - d under linlog, the five columns of row i are
+ *   GE_ENERGY_REP       1/2 repel m_i sum_{j != i} m_j / dh_ij
+ *   GE_ENERGY_ATT       1/2 attract sum_{k in row i} a'_ik psi(dh_ik), divided by m_i under
+ *                       nohubs (the stored entries as they are, self entries included, as
+ *                       the reference's loop takes them)
+ *   GE_ENERGY_GRAV      gravity m_i |x_i|_2
+ *   GE_ENERGY_PAIRDIST  sum_{j != i} d_ij   (unclamped; 0 for coincident points)
+ *   GE_ENERGY_EDGELEN   sum_{k in row i} d_ik   (unclamped, unweighted)
+ * and totals[c] is column c summed over the rows asked for.  E = totals[REP] + totals[ATT]
+ * + totals[GRAV]; for a symmetric graph with nohubs == 0, -dE/dx_i is the reference's
+ * force on i (include/forceatlas.hpp:146-211) wherever no pair is clamped and x_i != 0
+ * (tests/test_energy_cases.py checks it by central differences).  With nohubs, or inside
+ * the clamp, the reference's force is not a gradient; the values are defined all the
+ * same.  The relative edge length
+ *   lambda = (totals[EDGELEN] / nnz) / (totals[PAIRDIST] / (n (n - 1)))
+ * does not depend on the layout's scale: 1 for a random layout, well below 1 when
+ * neighbours are close.  The values ignore ks, ksmax, tolerate, normalize, seed, mode and
+ * theta: a plan of any mode, over any row range, and every rank of the sharded form give
+ * the same bits.  Every sum has one order: a row's partners in jb = max(1, min(16,
+ * ceil(n / 256))) chunks of ceil(n / jb), each chunk a chain over ascending j, the chunks
+ * added in order; a row's entries in stored order up to 64 entries, above that 64
+ * interleaved chains (entries l, l + 64, ...) added in order l = 0 .. 63; the totals in
+ * blocks of 1 024 consecutive rows (zeros past the last): ((v0 + v1) + (v2 + v3)) per
+ * four rows, the 256 sums folded in halves (a[t] += a[t + h], h = 128 .. 1), the block
+ * sums added in block order.
+ * Domain: GE_MODE_FAST's, finite coordinates whose squared differences do not overflow;
+ * squared differences that underflow (separations below ~1e-154) read as distance 0.  A
+ * vertex with a NaN or infinite coordinate has NaN in its five columns, puts NaN into
+ * REP and PAIRDIST of every other row and into ATT and EDGELEN of its neighbours, and so
+ * into the totals.
+ * The multilevel levels have no such energy (forceAtlasMultilevel's external pull is not
+ * conservative, :453-465): the yardstick of an embed is this energy of its output on the
+ * level-0 graph. */
+#define GE_ENERGY_COLS 5
+#define GE_ENERGY_REP 0
+#define GE_ENERGY_ATT 1
+#define GE_ENERGY_GRAV 2
+#define GE_ENERGY_PAIRDIST 3
+#define GE_ENERGY_EDGELEN 4
+/* d_x: n*dim coordinates (device).  d_rows: (row_end - row_begin)*5 doubles (device,
+ * row-major; may be NULL).  totals: 5 doubles (host), over the plan's rows.  Works on a
+ * plan of any mode; its buffers are allocated by the first call, and the plan is not
+ * disturbed: steps interleaved with energy calls give what they give without them.
+ * Synchronises. */
+int ge_fa_plan_energy(ge_fa_plan* plan, const double* d_x, double* d_rows, double* totals);
+/* The same from host arrays through a temporary plan: coords n*dim, rows n*5 (may be
+ * NULL), totals 5.  dim outside 1..16, n < 1, null coords or totals: GE_ERR_ARG. */
+int ge_layout_energy(ge_ctx* ctx, int n, const int* indptr, const int* indices,
+                     const double* data, int dim, const double* coords, const ge_fa_params* p,
+                     double* rows, double* totals);
+
 /* ---- multilevel ForceAtlas ----
  * Replaces partition::forceAtlasMultilevel(A, P, v_A, coords_A, r_A, coords,
  * dim, iterations, ks, ksmax, useWeights, linlog, nohubs, repel, attract,
@@ -643,6 +701,12 @@ int ge_allgather_members(ge_comm* comm, double* d_x, int dim, int m, const int* 
 int ge_force_atlas_dist(ge_comm* comm, int n, const int* indptr, const int* indices,
                         const double* data, int dim, double* coords, int init_random,
                         int iterations, const ge_fa_params* p);
+/* ge_layout_energy over row shards as ge_force_atlas_dist's: one all-gather of the per-row
+ * values, then every rank sums all n rows with the one-GPU call's kernel, so rows and
+ * totals have that call's bits on every rank. */
+int ge_layout_energy_dist(ge_comm* comm, int n, const int* indptr, const int* indices,
+                          const double* data, int dim, const double* coords,
+                          const ge_fa_params* p, double* rows, double* totals);
 int ge_force_atlas_ml_dist(ge_comm* comm, int n, const int* indptr, const int* indices,
                            const double* data, int m, const int* pt_indptr,
                            const int* pt_indices, const int* vertex_A, const double* coords_A,
