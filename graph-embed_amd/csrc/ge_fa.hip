@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "ge_energy.hpp"
+#include "ge_fa_sched.hpp"
 #include "ge_far.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
@@ -93,8 +94,6 @@ __global__ void degp1_kernel(int n, const int* __restrict__ ip, const double* __
 // added to each row's sum in j order (R*U = 8; few rows per CU, as on a row
 // shard of N GPUs, take small R and large U).
 
-constexpr int kRepThreads = 512;
-constexpr int kTileJ = 256;
 // Row slots x partners in flight per lane.  A lane holds xi, acc and the terms in
 // flight, D doubles each: 8 up to D = 4, then 2 and 1 so that the terms in flight stay
 // within 16 doubles and the kernel in registers.
@@ -232,10 +231,6 @@ fa_repulse_strict(int n, int rb, int re, int per_block, const double* __restrict
 // sum for its rows into Fpart[jb][row]; fa_reduce_parts sums the partials.
 // Pair term in closed form (fast_rep_pair, ge_pair.hpp): F_i += c_ij * (x_i - x_j) /
 // dis^3, 1 / dis from one rsqrt + two Newton steps, FMA everywhere.
-
-constexpr int kFastJBlocks = 16;  // j-range split
-
-constexpr int kFastThreads = 256;
 
 template <int D, int R>
 __global__ void __launch_bounds__(kFastThreads)
@@ -425,24 +420,7 @@ struct FaRows {
 // order -- the reference's serial sum, with G times the parallelism of one
 // lane per row (n = 127 gives 16 waves instead of 2).
 
-constexpr int kSmallMax = 512;  // one row group per thread group below
-// Above D = 4 (the wide schedule) the general kernel alone runs, with kSmallWideT
-// threads: 512 threads leave 256 registers per lane, and the kernel holds xi, acc, F
-// and fprev (D doubles each) beside a term.  Its rows are what the block's LDS leaves
-// for records after the term buffer of kSmallWideT x D doubles, at most one row per
-// thread: 256 at every D up to 16 (the LDS alone would allow 903 at D = 16).  Larger
-// levels take the fused step.
-constexpr int kSmallWideT = 256;
-constexpr int small_cap(int D) {
-  if (D <= kNarrowMaxDim) return kSmallMax;
-  const size_t rows = (kLdsBlock - sizeof(double) * kSmallWideT * D) / (sizeof(double) * rec_width(D));
-  return rows < (size_t)kSmallWideT ? (int)rows : kSmallWideT;
-}
-static_assert(small_cap(5) == 256 && small_cap(16) == 256, "one row per thread fits at every D");
-constexpr int kSmallDefault = 64;
-constexpr int kSmallNnz = 6144;
-// CSR entries staged in LDS (the 4-D double-buffered term tile leaves less room)
-constexpr int small_nnz_cap(int D) { return D == 4 ? 4096 : kSmallNnz; }
+// (kSmallMax, small_cap and the other bounds of these kernels: ge_fa_sched.hpp)
 
 // The G lanes of a group hold U terms each (term u of lane g is partner
 // g + G*u of the chunk); the group's first lane adds the first cnt in order.
@@ -756,75 +734,69 @@ fa_small_strict(int n, const int* __restrict__ ip, const int* __restrict__ ixg,
   if (DOMAIN_ONLY && tid == 0) *it_state = it;
 }
 
-// lanes per row for n rows in a T-thread workgroup
-inline int small_group(int n, int T) {
-  if (const char* e = std::getenv("GE_SMALL_G")) {  // tuning override
-    const int g = std::atoi(e);
-    if ((g == 1 || g == 2 || g == 4 || g == 8 || g == 16) && n * g <= T) return g;
+// The compile-time forms of what a schedule (ge_fa_sched.hpp) chose at run time:
+// f(integral_constant<int, g>) for g a power of two up to Max (lanes per row, row slots;
+// the schedule gives nothing else: its knobs are validated in fa_knobs_from_env) ...
+template <int Max, class F>
+void dispatch_pow2(int g, F&& f) {
+  if constexpr (Max > 1) {
+    if (g < Max) return dispatch_pow2<Max / 2>(g, f);
   }
-  int G = 1;
-  while (G < 16 && n * G * 2 <= T) G *= 2;
-  return G;
+  f(std::integral_constant<int, Max>());
 }
 
-constexpr int kSmallFastT = 1024;  // domain-only kernel
-constexpr int kSmallGenT = 512;    // general kernel
+// ... and f(REPEL_ONE, LINEAR) for the kernels' two body flags.
+template <class F>
+void dispatch_body(bool repel_one, bool linear, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (repel_one) {
+    if (linear) f(T(), T());
+    else f(T(), N());
+  } else {
+    if (linear) f(N(), T());
+    else f(N(), N());
+  }
+}
 
-// Fp: n*D scratch, it_state: one int (device).
+// ge_force_atlas's one-workgroup run (FaRunSched::small).  Fp: n*D scratch, it_state: one
+// int (device).  Narrow: the domain-only kernel (where the schedule runs it) hands over to
+// the general one at r.small_handover.  wide: the general kernel from iteration 0 (both
+// bodies, CSR read from global memory), kSmallWideT threads, 1, 2 or 8 lanes per row.
 template <int D>
-void launch_small(hipStream_t s, int n, int nnz, const int* ip, const int* ix, const double* dx,
-                  const double* dp1, double* X, double* Fp, int* it_state, int iterations,
-                  const FaConst& c) {
+void launch_small(hipStream_t s, const FaRunSched& r, bool wide, int n, const int* ip,
+                  const int* ix, const double* dx, const double* dp1, double* X, double* Fp,
+                  int* it_state, int iterations, const FaConst& c) {
   GE_HIP(hipMemsetAsync(Fp, 0, sizeof(double) * (size_t)n * D, s));
   GE_HIP(hipMemsetAsync(it_state, 0, sizeof(int), s));
-  const bool staged = nnz <= small_nnz_cap(D);
-  int stop_at = iterations;  // test hook: hand over to the general kernel there
-  if (const char* e = std::getenv("GE_SMALL_HANDOVER")) stop_at = std::atoi(e);
   auto go = [&](auto GG, auto TT, auto ST, auto DO) {
     hipLaunchKernelGGL((fa_small_strict<D, decltype(GG)::value, decltype(TT)::value,
                                         decltype(ST)::value, decltype(DO)::value>),
                        dim3(1), dim3(decltype(TT)::value), 0, s, n, ip, ix, dx, dp1, X, Fp,
-                       it_state, iterations, stop_at, c);
+                       it_state, iterations, r.small_handover, c);
   };
   using F = std::false_type;
   using Tt = std::true_type;
-  auto by_group = [&](int G, auto TT, auto DO) {
-    auto by_stage = [&](auto GG) {
-      if (staged) go(GG, TT, Tt(), DO);
-      else go(GG, TT, F(), DO);
-    };
-    switch (G) {
-      case 16: by_stage(std::integral_constant<int, 16>()); break;
-      case 8: by_stage(std::integral_constant<int, 8>()); break;
-      case 4: by_stage(std::integral_constant<int, 4>()); break;
-      case 2: by_stage(std::integral_constant<int, 2>()); break;
-      default: by_stage(std::integral_constant<int, 1>()); break;
+  if (wide || D > kNarrowMaxDim) {
+    const auto TT = std::integral_constant<int, kSmallWideT>();
+    switch (r.small_g_general) {
+      case 8: go(std::integral_constant<int, 8>(), TT, F(), F()); break;
+      case 2: go(std::integral_constant<int, 2>(), TT, F(), F()); break;
+      default: go(std::integral_constant<int, 1>(), TT, F(), F()); break;
     }
-  };
-  // the domain-only kernel has the linear attraction only (linlog == 0, delta == 1)
-  if (!std::getenv("GE_SMALL_GENERAL_ONLY") && !c.linlog && c.delta == 1.0)
-    by_group(small_group(n, kSmallFastT), std::integral_constant<int, kSmallFastT>(), Tt());
-  by_group(small_group(n, kSmallGenT), std::integral_constant<int, kSmallGenT>(), F());
-}
-
-// The wide schedule's one-workgroup run: the general kernel from iteration 0 (both
-// bodies, CSR read from global memory), kSmallWideT threads, 1, 2 or 8 lanes per row.
-inline int small_wide_cap(int D) { return std::min(small_cap(D), kSmallWideT); }
-template <int D>
-void launch_small_wide(hipStream_t s, int n, const int* ip, const int* ix, const double* dx,
-                       const double* dp1, double* X, double* Fp, int* it_state, int iterations,
-                       const FaConst& c) {
-  GE_HIP(hipMemsetAsync(Fp, 0, sizeof(double) * (size_t)n * D, s));
-  GE_HIP(hipMemsetAsync(it_state, 0, sizeof(int), s));
-  auto go = [&](auto GG) {
-    hipLaunchKernelGGL((fa_small_strict<D, decltype(GG)::value, kSmallWideT, false, false>),
-                       dim3(1), dim3(kSmallWideT), 0, s, n, ip, ix, dx, dp1, X, Fp, it_state,
-                       iterations, iterations, c);
-  };
-  const int G = small_group(n, kSmallWideT);  // n G <= kSmallWideT
-  if (G >= 8) go(std::integral_constant<int, 8>());
-  else if (G >= 2) go(std::integral_constant<int, 2>());
-  else go(std::integral_constant<int, 1>());
+    return;
+  }
+  if constexpr (D <= kNarrowMaxDim) {
+    auto by_group = [&](int G, auto TT, auto DO) {
+      dispatch_pow2<16>(G, [&](auto GG) {
+        if (r.small_staged) go(GG, TT, Tt(), DO);
+        else go(GG, TT, F(), DO);
+      });
+    };
+    if (r.small_g_domain)
+      by_group(r.small_g_domain, std::integral_constant<int, kSmallFastT>(), Tt());
+    by_group(r.small_g_general, std::integral_constant<int, kSmallGenT>(), F());
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -893,18 +865,7 @@ __device__ __forceinline__ bool stage_records(const double* __restrict__ X,
 #endif
 constexpr bool kBarCohStage = GE_BAR_ORDER < 3;
 
-constexpr int kGrpT = 256;
-// LDS of the fused step: the records (rec_width(D) doubles each), then the two term
-// buffers of kGrpT x D doubles.  The records get what the block's LDS leaves after the
-// term buffers, at most 96 KiB: 3072 records at D <= 3, 1536 at D = 4..7, 675 at D = 16.
-constexpr size_t grouped_tb_bytes(int D) { return sizeof(double) * 2 * kGrpT * D; }
-constexpr size_t grouped_rec_budget(int D) {
-  return kLdsBlock - grouped_tb_bytes(D) < 96 * 1024 ? kLdsBlock - grouped_tb_bytes(D) : 96 * 1024;
-}
-constexpr int grouped_cap(int D) {
-  return (int)(grouped_rec_budget(D) / (sizeof(double) * rec_width(D)));
-}
-static_assert(grouped_cap(3) == 3072 && grouped_cap(4) == 1536, "the D <= 4 caps are unchanged");
+// (kGrpT and grouped_cap, the records the fused step holds in LDS: ge_fa_sched.hpp)
 inline size_t grouped_lds_bytes(int n, int D) {
   return sizeof(double) * (size_t)n * rec_width(D) + grouped_tb_bytes(D);
 }
@@ -1383,12 +1344,6 @@ constexpr int stream_tile(int D) {
   return grouped_cap(D) >= 2048 || D <= kNarrowMaxDim ? 2048 : grouped_cap(D) / 256 * 256;
 }
 static_assert(stream_tile(16) >= 256, "a tile of at least one round of the block");
-constexpr int kStreamMax = 65536;
-// GE_STREAM_MAX overrides the bound (tuning / tests)
-inline int stream_max() {
-  if (const char* e = std::getenv("GE_STREAM_MAX")) return std::atoi(e);
-  return kStreamMax;
-}
 inline size_t stream_lds_bytes(int D) { return grouped_lds_bytes(stream_tile(D), D); }
 
 template <int D, int G, bool REPEL_ONE, bool LINEAR>
@@ -1486,135 +1441,61 @@ fa_grouped_stream(int n, int rb, int re, const int* __restrict__ ip, const int* 
 // ---------------------------------------------------------------------------
 // host-side launch helpers
 
-constexpr int kRowsPerThreadFast = 4;
-
-// GE_MODE_FARFIELD: the smallest level that runs the far field and the rows of a work
-// item (64 R), both from measurement (plan_init; DESIGN.md, FARFIELD mode).
-constexpr int kFarMinDefault = 131072;
-constexpr int kFarItemRows = 64;
-
-// Lanes per row of the small-level kernels.
-inline int grouped_lanes(int rows) {
-  int G = 1;  // lanes per row: aim for >= 128 K lanes, at most one wave per row
-  while (G < 64 && (long long)rows * G < 131072) G *= 2;  // n = 4373: G = 32 (175 us, G = 16: 211)
-  if (const char* e = std::getenv("GE_GRP_G")) {  // tuning / test override
-    const int g = std::atoi(e);
-    if (g >= 1 && g <= 64 && (g & (g - 1)) == 0) G = g;
-  }
-  return G;
-}
-
-// fa_repulse_strict's grid: one block per CU, rows split evenly (rounded to whole
-// 64-row wave slots).  GE_REP_BLOCKS caps the blocks (tests).
-inline void rep_grid(int rows, int cus, int& per, int& nb) {
-  int cap = cus;
-  if (const char* e = std::getenv("GE_REP_BLOCKS")) cap = std::max(1, std::atoi(e));  // tests
-  const int blocks = std::max(1, std::min(cap, (rows + 63) / 64));
-  per = (rows + blocks - 1) / blocks;
-  per = (per + 63) / 64 * 64;
-  nb = (rows + per - 1) / per;
-}
-
-// The schedules of D <= kNarrowMaxDim.
+// One repulsion pass of kind `rep` (GE_FA_REP_GROUPED, _ORDERED, _ORDERED_WIDE or _FAST)
+// with the grid, lanes and row slots of the plan's schedule.
 template <int D>
-void launch_repulsion_narrow(hipStream_t s, int mode, int n, int rb, int re, const double* X,
-                             const double* dp1, double repel, double* Frep, double* Fpart,
-                             int cus) {
-  const int rows = re - rb;
-  if (mode == GE_MODE_FAST) {
-    const int per = kFastThreads * kRowsPerThreadFast;
-    const int jb = std::max(1, std::min(kFastJBlocks, (n + kTileJ - 1) / kTileJ));
-    dim3 grid((rows + per - 1) / per, jb);
-    hipLaunchKernelGGL((fa_repulse_fast<D, kRowsPerThreadFast>), grid, dim3(kFastThreads), 0, s,
-                       n, rb, re, X, dp1, repel, jb, Fpart);
-    const int tot = rows * D;
-    hipLaunchKernelGGL((fa_reduce_parts<D>), dim3((tot + 255) / 256), dim3(256), 0, s, rows, jb,
-                       Fpart, Frep);
-    return;
-  }
-  if (n <= grouped_cap(D)) {
-    const int G = grouped_lanes(rows);
-    auto go = [&](auto GG) {
-      constexpr int GC = decltype(GG)::value;
-      const int nb = (rows + kGrpT / GC - 1) / (kGrpT / GC);
-      const size_t lds = grouped_lds_bytes(n, D);
-      if (lds > 65536) {  // above the default dynamic-LDS limit
-        GE_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&fa_repulse_grouped<D, GC, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GE_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&fa_repulse_grouped<D, GC, false>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      }
-      if (repel == 1.0)
-        hipLaunchKernelGGL((fa_repulse_grouped<D, GC, true>), dim3(nb), dim3(kGrpT), lds, s, n,
-                           rb, re, X, dp1, repel, Frep);
-      else
-        hipLaunchKernelGGL((fa_repulse_grouped<D, GC, false>), dim3(nb), dim3(kGrpT), lds, s, n,
-                           rb, re, X, dp1, repel, Frep);
-    };
-    switch (G) {
-      case 64: go(std::integral_constant<int, 64>()); break;
-      case 32: go(std::integral_constant<int, 32>()); break;
-      case 16: go(std::integral_constant<int, 16>()); break;
-      case 8: go(std::integral_constant<int, 8>()); break;
-      case 4: go(std::integral_constant<int, 4>()); break;
-      case 2: go(std::integral_constant<int, 2>()); break;
-      default: go(std::integral_constant<int, 1>()); break;
-    }
-    return;
-  }
-  int per, nb;
-  rep_grid(rows, cus, per, nb);
-  // Row slots per lane.  Measured at C2 size (scripts/shard_tune.py, rows of
-  // an N-GPU shard): with more than 1024 rows per block 8 slots x 1 partner is
-  // fastest (500 K rows: 581 against 563 Gpairs/s for R = 1); at 1024 and below
-  // 1 slot x 8 partners (250 K rows: R = 1 566, R = 8 551; 125 K rows: R = 1
-  // 565 Gpairs/s).
-  int R = per > 2 * kRepThreads ? 8 : 1;
-  if (const char* e = std::getenv("GE_REP_R")) {  // tuning / test override
-    const int r = std::atoi(e);
-    if (r == 1 || r == 2 || r == 4 || r == 8) R = r;
-  }
-  auto go = [&](auto RR) {
-    constexpr int RC = decltype(RR)::value;
-    if (repel == 1.0)
-      hipLaunchKernelGGL((fa_repulse_strict<D, true, RC>), dim3(nb), dim3(kRepThreads), 0, s, n,
-                         rb, re, per, X, dp1, repel, Frep);
-    else
-      hipLaunchKernelGGL((fa_repulse_strict<D, false, RC>), dim3(nb), dim3(kRepThreads), 0, s, n,
-                         rb, re, per, X, dp1, repel, Frep);
-  };
-  switch (R) {
-    case 8: go(std::integral_constant<int, 8>()); break;
-    case 4: go(std::integral_constant<int, 4>()); break;
-    case 2: go(std::integral_constant<int, 2>()); break;
-    default: go(std::integral_constant<int, 1>()); break;
-  }
-}
-
-// wide: the ordered-pair kernel at every size, one row slot per lane (ge_pair.hpp).
-template <int D>
-void launch_repulsion(hipStream_t s, int mode, int n, int rb, int re, const double* X,
-                      const double* dp1, double repel, double* Frep, double* Fpart, int cus,
-                      bool wide) {
+void launch_repulsion(hipStream_t s, const FaSched& sc, int rep, int n, int rb, int re,
+                      const double* X, const double* dp1, double repel, double* Frep,
+                      double* Fpart) {
   const int rows = re - rb;
   if (rows <= 0) return;
-  if (wide || D > kNarrowMaxDim) {
-    int per, nb;
-    rep_grid(rows, cus, per, nb);
-    hipLaunchKernelGGL((fa_repulse_strict<D, false, 1>), dim3(nb), dim3(kRepThreads), 0, s, n, rb,
-                       re, per, X, dp1, repel, Frep);
+  if (rep == GE_FA_REP_ORDERED_WIDE) {
+    hipLaunchKernelGGL((fa_repulse_strict<D, false, 1>), dim3(sc.nb), dim3(kRepThreads), 0, s, n,
+                       rb, re, sc.per, X, dp1, repel, Frep);
     return;
   }
-  if constexpr (D <= kNarrowMaxDim)
-    launch_repulsion_narrow<D>(s, mode, n, rb, re, X, dp1, repel, Frep, Fpart, cus);
+  if constexpr (D <= kNarrowMaxDim) {
+    if (rep == GE_FA_REP_FAST) {
+      hipLaunchKernelGGL((fa_repulse_fast<D, kRowsPerThreadFast>), dim3(sc.fast_blocks, sc.fast_jb),
+                         dim3(kFastThreads), 0, s, n, rb, re, X, dp1, repel, sc.fast_jb, Fpart);
+      const int tot = rows * D;
+      hipLaunchKernelGGL((fa_reduce_parts<D>), dim3((tot + 255) / 256), dim3(256), 0, s, rows,
+                         sc.fast_jb, Fpart, Frep);
+    } else if (rep == GE_FA_REP_GROUPED) {
+      dispatch_pow2<64>(sc.lanes, [&](auto GG) {
+        constexpr int GC = decltype(GG)::value;
+        const int nb = (rows + kGrpT / GC - 1) / (kGrpT / GC);
+        const size_t lds = grouped_lds_bytes(n, D);
+        if (lds > 65536) {  // above the default dynamic-LDS limit
+          GE_HIP(hipFuncSetAttribute(
+              reinterpret_cast<const void*>(&fa_repulse_grouped<D, GC, true>),
+              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          GE_HIP(hipFuncSetAttribute(
+              reinterpret_cast<const void*>(&fa_repulse_grouped<D, GC, false>),
+              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        dispatch_body(sc.repel_one, false, [&](auto RO, auto) {
+          hipLaunchKernelGGL((fa_repulse_grouped<D, GC, decltype(RO)::value>), dim3(nb),
+                             dim3(kGrpT), lds, s, n, rb, re, X, dp1, repel, Frep);
+        });
+      });
+    } else {
+      dispatch_pow2<8>(sc.R, [&](auto RR) {
+        dispatch_body(sc.repel_one, false, [&](auto RO, auto) {
+          hipLaunchKernelGGL((fa_repulse_strict<D, decltype(RO)::value, decltype(RR)::value>),
+                             dim3(sc.nb), dim3(kRepThreads), 0, s, n, rb, re, sc.per, X, dp1, repel,
+                             Frep);
+        });
+      });
+    }
+  }
 }
 
 // Small levels (n <= grouped_cap: fa_grouped_step) and mid-size ones (n <=
 // stream_max: fa_grouped_stream): one launch per iteration.
 struct GroupedArgs {
   hipStream_t s;
+  bool stream;  // FaSched::step == GE_FA_STEP_STREAM
   int n, rb, re;
   const int *ip, *ix;
   const double *dx, *X, *dp1;
@@ -1625,14 +1506,13 @@ struct GroupedArgs {
 template <int D, int GC, bool R1, bool LIN>
 void launch_grouped_variant(const GroupedArgs& a) {
   const int rows = a.re - a.rb;
-  const bool stream = a.n > grouped_cap(D);
-  const size_t lds = stream ? stream_lds_bytes(D) : grouped_lds_bytes(a.n, D);
+  const size_t lds = a.stream ? stream_lds_bytes(D) : grouped_lds_bytes(a.n, D);
   const int nb = (rows + kGrpT / GC - 1) / (kGrpT / GC);
-  const void* fn = stream ? reinterpret_cast<const void*>(&fa_grouped_stream<D, GC, R1, LIN>)
-                          : reinterpret_cast<const void*>(&fa_grouped_step<D, GC, R1, LIN>);
+  const void* fn = a.stream ? reinterpret_cast<const void*>(&fa_grouped_stream<D, GC, R1, LIN>)
+                            : reinterpret_cast<const void*>(&fa_grouped_step<D, GC, R1, LIN>);
   if (lds > 65536)  // above the default dynamic-LDS limit
     GE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (stream)
+  if (a.stream)
     hipLaunchKernelGGL((fa_grouped_stream<D, GC, R1, LIN>), dim3(nb), dim3(kGrpT), lds, a.s, a.n,
                        a.rb, a.re, a.ip, a.ix, a.dx, a.X, a.dp1, a.c, a.Fprev, a.Xnext);
   else
@@ -1640,45 +1520,23 @@ void launch_grouped_variant(const GroupedArgs& a) {
                        a.rb, a.re, a.ip, a.ix, a.dx, a.X, a.dp1, a.c, a.Fprev, a.Xnext);
 }
 
-// D <= kNarrowMaxDim: every group size, the repel == 1 and linear-attraction bodies.
+// The fused step.  D <= kNarrowMaxDim: every group size, the repel == 1 and
+// linear-attraction bodies.  wide (ge_pair.hpp): the general bodies in two group sizes.
 template <int D>
-void launch_grouped_step_narrow(const GroupedArgs& a) {
-  auto go = [&](auto GG) {
-    constexpr int GC = decltype(GG)::value;
-    const bool lin = !a.c.linlog && a.c.delta == 1.0;
-    if (a.c.repel == 1.0) {
-      if (lin) launch_grouped_variant<D, GC, true, true>(a);
-      else launch_grouped_variant<D, GC, true, false>(a);
-    } else {
-      if (lin) launch_grouped_variant<D, GC, false, true>(a);
-      else launch_grouped_variant<D, GC, false, false>(a);
-    }
-  };
-  switch (grouped_lanes(a.re - a.rb)) {
-    case 64: go(std::integral_constant<int, 64>()); break;
-    case 32: go(std::integral_constant<int, 32>()); break;
-    case 16: go(std::integral_constant<int, 16>()); break;
-    case 8: go(std::integral_constant<int, 8>()); break;
-    case 4: go(std::integral_constant<int, 4>()); break;
-    case 2: go(std::integral_constant<int, 2>()); break;
-    default: go(std::integral_constant<int, 1>()); break;
-  }
-}
-
-// wide (ge_pair.hpp): the general bodies (same bits as their specialisations) in two
-// group sizes, a wave per row below 8192 rows (grouped_lanes 32 or 64), else 8 lanes.
-template <int D>
-void launch_grouped_step(hipStream_t s, int n, int rb, int re, const int* ip, const int* ix,
-                         const double* dx, const double* X, const double* dp1, const FaConst& c,
-                         double* Fprev, double* Xnext, bool wide) {
-  if (re - rb <= 0) return;
-  const GroupedArgs a{s, n, rb, re, ip, ix, dx, X, dp1, c, Fprev, Xnext};
-  if (wide || D > kNarrowMaxDim) {
-    if (grouped_lanes(re - rb) >= 32) launch_grouped_variant<D, 64, false, false>(a);
+void launch_grouped_step(const FaSched& sc, const GroupedArgs& a) {
+  if (a.re - a.rb <= 0) return;
+  if (sc.wide || D > kNarrowMaxDim) {
+    if (sc.lanes == 64) launch_grouped_variant<D, 64, false, false>(a);
     else launch_grouped_variant<D, 8, false, false>(a);
     return;
   }
-  if constexpr (D <= kNarrowMaxDim) launch_grouped_step_narrow<D>(a);
+  if constexpr (D <= kNarrowMaxDim)
+    dispatch_pow2<64>(sc.lanes, [&](auto GG) {
+      dispatch_body(sc.repel_one, sc.linear, [&](auto RO, auto LI) {
+        launch_grouped_variant<D, decltype(GG)::value, decltype(RO)::value,
+                               decltype(LI)::value>(a);
+      });
+    });
 }
 
 template <int D>
@@ -1708,13 +1566,15 @@ struct ge_fa_plan {
   ge::RowClasses rc;
   ge::RowStreams rstreams;
   int cus = 256;
-  bool wide = false;  // the wide schedule (ge_pair.hpp): dim > 4, or GE_WIDE_MIN_DIM
+  // which kernels the step and the repulsion pass launch, settled by plan_init
+  // (ge_fa_sched.hpp), and what it was made from
+  ge::FaSchedIn sched_in;
+  ge::FaSched sched;
   bool profiling = false;
   ge::EventPool events{3 * 64};  // 3 per timed step
   // Symmetric repulsion (ge_sym.hpp) for a whole large level in STRICT mode: the n
   // vertices as one "aggregate" of T = ceil(n / 64) row tiles, every unordered pair
-  // evaluated once.  ctl = {queue, prog[T]}, zeroed before every launch.
-  bool sym = false;
+  // evaluated once (sched.sym).  ctl = {queue, prog[T]}, zeroed before every launch.
   int sym_units = 0, sym_blocks = 0;
   long long sym_limit = 0;
   ge::DevBuf<int4> units;
@@ -1722,9 +1582,8 @@ struct ge_fa_plan {
   ge::DevBuf<double> hand;
   int* sym_err_h = nullptr;  // pinned, device-mapped: a timed-out hand-over wait
   int* sym_err_d = nullptr;
-  // GE_MODE_FARFIELD (ge_far.hip): the engine when the far field runs, else why not
+  // GE_MODE_FARFIELD (ge_far.hip): the engine when the far field runs (sched.far_reason)
   ge::FarEngine* far = nullptr;
-  int far_reason = GE_FAR_NOT_REQUESTED;
   // ge_fa_plan_energy's buffers, made by its first call (ge_energy.hpp)
   std::unique_ptr<ge::EnergyScratch> energy;
   ~ge_fa_plan() {
@@ -1735,14 +1594,28 @@ struct ge_fa_plan {
 
 namespace ge {
 
-static void plan_init(ge_fa_plan* pl) {
+// What the schedule takes from a plan's arguments, the device (cus) and the environment.
+static FaSchedIn plan_sched_in(int n, int rb, int re, int dim, const ge_fa_params& p, int cus) {
+  FaSchedIn in;
+  in.n = n;
+  in.rb = rb;
+  in.re = re;
+  in.dim = dim;
+  in.mode = p.mode;
+  in.repel_one = p.repel == 1.0;
+  in.linear = !p.linlog && p.delta == 1.0;
+  in.wide = wide_dim(dim);
+  in.cus = cus;
+  in.knobs = fa_knobs_from_env();
+  return in;
+}
+
+static void plan_init(ge_fa_plan* pl, const FaSchedIn& in) {
   const int rows = pl->re - pl->rb;
-  pl->cus = device_cus();
-  pl->wide = wide_dim(pl->dim);
   check_far_params(pl->p);
-  const bool far_req = pl->p.mode == GE_MODE_FARFIELD;
-  // FAST is a tolerance-only mode and has no wide kernels: the exact ones satisfy it
-  if (pl->wide) pl->p.mode = GE_MODE_STRICT;
+  pl->sched_in = in;
+  pl->sched = fa_schedule(pl->sched_in);
+  pl->cus = pl->sched_in.cus;
   pl->dp1.alloc(pl->n);
   pl->frep.alloc((size_t)std::max(rows, 1) * pl->dim);
   pl->fprev.alloc((size_t)std::max(rows, 1) * pl->dim);
@@ -1768,40 +1641,17 @@ static void plan_init(ge_fa_plan* pl) {
   hipLaunchKernelGGL(degp1_kernel, dim3((pl->n + 255) / 256), dim3(256), 0, s, pl->n, pl->ip,
                      pl->dx, pl->p.use_weights, pl->dp1.p);
   GE_HIP(hipGetLastError());
-  // The far field runs for a whole narrow level with positive masses from far_min
-  // vertices up; every other FARFIELD plan is a FAST plan (include/ge.h).  far_min: the
-  // smallest power of two from 2^13 at which FARFIELD beat FAST at d = 3, theta = 0.5 on
-  // an MI355X is 2^17 (ms per step, FAST / FARFIELD: 2^16 3.5 / 5.9, 2^17 13.9 / 12.0-12.5,
-  // 2^18 50 / 25-27, 2^20 780 / 112-116; profiles/r13/farfield_crossover.jsonl);
-  // GE_FAR_MIN overrides.  Items of 64 rows: 108-112 ms per C2 step against 231-268
-  // for 256 rows (same log; GE_FAR_R=1|4 overrides, tests and tuning).
-  if (far_req) {
-    int far_min = kFarMinDefault;
-    if (const char* e = std::getenv("GE_FAR_MIN")) far_min = std::atoi(e);
-    int item_rows = kFarItemRows;
-    if (const char* e = std::getenv("GE_FAR_R")) item_rows = std::atoi(e) == 1 ? 64 : std::atoi(e) == 4 ? 256 : item_rows;
-    pl->far_reason = pl->wide || pl->dim > kNarrowMaxDim ? GE_FAR_DIM
-                     : pl->rb != 0 || pl->re != pl->n    ? GE_FAR_ROW_SHARD
-                     : !far_masses_ok(s, pl->n, pl->dp1.p) ? GE_FAR_MASS
-                     : pl->n < far_min                    ? GE_FAR_SMALL
-                                                          : GE_FAR_ACTIVE;
-    if (pl->far_reason == GE_FAR_ACTIVE)
-      pl->far = far_create(s, pl->n, pl->dim, pl->p.theta, item_rows, pl->cus);
-    else if (pl->p.mode == GE_MODE_FARFIELD)
-      pl->p.mode = GE_MODE_FAST;
+  // the far field's masses are on the device: where the schedule rests on them, ask
+  if (pl->sched.far_mass_check && !far_masses_ok(s, pl->n, pl->dp1.p)) {
+    pl->sched_in.masses_ok = false;
+    pl->sched = fa_schedule(pl->sched_in);
   }
-  if (pl->p.mode == GE_MODE_FAST || pl->far)  // the far field's non-finite iterations run FAST
+  pl->p.mode = pl->sched.mode;
+  if (pl->sched.far_reason == GE_FAR_ACTIVE)
+    pl->far = far_create(s, pl->n, pl->dim, pl->p.theta, pl->sched.far_item_rows, pl->cus);
+  if (pl->sched.fpart)
     pl->fpart.alloc((size_t)std::max(rows, 1) * pl->dim * kFastJBlocks);
   GE_HIP(hipMemsetAsync(pl->fprev.p, 0, sizeof(double) * pl->fprev.n, s));
-  // Symmetric repulsion: STRICT, every row on this plan (a row shard keeps the
-  // ordered-pair kernel), and a level past the grouped / streamed kernels.
-  // GE_FA_SYM=0 keeps fa_repulse_strict (comparisons), GE_FA_SYM=1 forces it.
-  {
-    const char* e = std::getenv("GE_FA_SYM");
-    const bool force = e && *e == '1', off = e && *e == '0';
-    pl->sym = !off && !pl->wide && pl->p.mode == GE_MODE_STRICT && pl->rb == 0 &&
-              pl->re == pl->n && (force || pl->n > stream_max());
-  }
   // (Round 4 also built a degree-ordered gather copy of the coordinates for the
   // neighbour gathers: C2 0.324 against 0.301 ms per pass, C5 31.8 against 30.3 ms;
   // removed in round 5)
@@ -1812,7 +1662,7 @@ static void plan_init(ge_fa_plan* pl) {
 // fa_run_device), so every symmetric plan holds them, one used only for
 // ge_fa_plan_attract included; the step's call is a no-op then.
 static void sym_prepare(ge_fa_plan* pl) {
-  if (!pl->sym || pl->sym_units > 0) return;
+  if (!pl->sched.sym || pl->sym_units > 0) return;
   hipStream_t s = pl->ctx->stream;
   {
     const int T = (pl->n + 63) / 64;
@@ -1848,22 +1698,26 @@ static void sym_check(ge_fa_plan* pl) {
   }
 }
 
-// The repulsion launch of one iteration into frep (rows [rb, re)): the symmetric
-// sweeps, the far field (FAST's kernels in an iteration whose box is not finite) or
-// the mode's ordered-pair kernels.
+// The repulsion launch of one iteration into frep (rows [rb, re)), as scheduled: the
+// symmetric sweeps, the far field (FAST's kernels in an iteration whose box is not
+// finite) or the mode's ordered-pair kernels.
 template <int D>
 static void plan_repulse_into(ge_fa_plan* pl, hipStream_t s, const double* xc, double* frep) {
-  if (pl->sym) {  // never on the wide schedule (plan_init)
+  const FaSched& sc = pl->sched;
+  if (sc.rep == GE_FA_REP_SWEEPS) {  // never on the wide schedule
     sym_prepare(pl);
     sym_check(pl);
     GE_HIP(hipMemsetAsync(pl->ctl.p, 0, sizeof(int) * pl->ctl.n, s));
     sym_repulse_launch(D, pl->sym_blocks, s, pl->sym_units, pl->units.p, pl->ctl.p, pl->seg.p, xc,
                        pl->dp1.p, pl->p.repel, frep, pl->hand.p, (size_t)pl->n, pl->ctl.p + 1,
                        pl->sym_err_d, pl->sym_limit);
-  } else if (pl->far && far_repulse(pl->far, s, xc, pl->dp1.p, pl->p.repel, frep)) {
+  } else if (sc.rep == GE_FA_REP_FARFIELD) {
+    if (!far_repulse(pl->far, s, xc, pl->dp1.p, pl->p.repel, frep))
+      launch_repulsion<D>(s, sc, GE_FA_REP_FAST, pl->n, pl->rb, pl->re, xc, pl->dp1.p,
+                          pl->p.repel, frep, pl->fpart.p);
   } else {
-    launch_repulsion<D>(s, pl->far ? GE_MODE_FAST : pl->p.mode, pl->n, pl->rb, pl->re, xc,
-                        pl->dp1.p, pl->p.repel, frep, pl->fpart.p, pl->cus, pl->wide);
+    launch_repulsion<D>(s, sc, sc.rep, pl->n, pl->rb, pl->re, xc, pl->dp1.p, pl->p.repel, frep,
+                        pl->fpart.p);
   }
 }
 
@@ -1873,9 +1727,10 @@ static void plan_step(ge_fa_plan* pl, const double* xc, double* xn) {
   if (ev) GE_HIP(hipEventRecord(ev[0], s));
   dispatch_dim(pl->dim, [&](auto Dc) {
     constexpr int D = decltype(Dc)::value;
-    if (pl->p.mode == GE_MODE_STRICT && pl->n <= stream_max() && !std::getenv("GE_GRP_SPLIT")) {
-      launch_grouped_step<D>(s, pl->n, pl->rb, pl->re, pl->ip, pl->ix, pl->dx, xc, pl->dp1.p,
-                             pl->c, pl->fprev.p, xn, pl->wide);
+    if (pl->sched.step != GE_FA_STEP_SPLIT) {
+      launch_grouped_step<D>(pl->sched, {s, pl->sched.step == GE_FA_STEP_STREAM, pl->n, pl->rb,
+                                         pl->re, pl->ip, pl->ix, pl->dx, xc, pl->dp1.p, pl->c,
+                                         pl->fprev.p, xn});
       if (ev) GE_HIP(hipEventRecord(ev[1], s));
       return;
     }
@@ -1915,15 +1770,16 @@ static void plan_attract(ge_fa_plan* pl, const double* xc, const double* frep, d
 // caller runs the per-iteration path from it.  Returns false (nothing computed)
 // when no G fits, the launch is refused or the barrier timed out;
 // GE_PERSIST_REQUIRE=1 (tests) makes each of these an error.  The result is in
-// Xa for an even iteration count, in Xb for an odd one.
-constexpr int kPersistMin = 128;  // fewer iterations: per-iteration launches
+// Xa for an even iteration count, in Xb for an odd one.  Called where the run's schedule
+// tries it (FaRunSched::persist); of the environment it reads the plan's knobs only.
 template <int D>
-bool launch_persistent(ge_fa_plan* pl, double* Xa, double* Xb, int iterations) {
+bool launch_persistent(ge_fa_plan* pl, const FaRunSched& run, double* Xa, double* Xb,
+                       int iterations) {
   const int n = pl->n;
-  if (n > grouped_cap(D) || pl->rb != 0 || pl->re != n) return false;
+  const FaKnobs& knobs = pl->sched_in.knobs;
   hipStream_t s = pl->ctx->stream;
   // 64 lanes per row: the packed rows (packed_iteration) unless GE_FA_PACKED=0
-  const bool packed_on = !(std::getenv("GE_FA_PACKED") && *std::getenv("GE_FA_PACKED") == '0');
+  const bool packed_on = run.packed;
   bool launched = false, fits = false, refused = false;
   DevBuf<int> bar;
   // the start state, restored when the barrier times out: taken only once a fitting
@@ -1969,8 +1825,8 @@ bool launch_persistent(ge_fa_plan* pl, double* Xa, double* Xb, int iterations) {
         return o;
       };
       int R = pk ? 4 : 0;
-      if (const char* e = std::getenv("GE_FA_PACK_ROWS"); pk && e)
-        R = std::atoi(e) == 6 ? 6 : 4;
+      if (pk && run.pack_rows)
+        R = run.pack_rows;
       else if (pk && (long long)((n + 3) / 4) > (long long)occupancy(4) * pl->cus)
         R = 6;
       const int nbk = pk ? (n + R - 1) / R : nb;
@@ -2006,30 +1862,10 @@ bool launch_persistent(ge_fa_plan* pl, double* Xa, double* Xb, int iterations) {
       GE_HIP(e);
       launched = true;
     };
-    const bool lin = !pl->c.linlog && pl->c.delta == 1.0;
-    using T = std::true_type;
-    using F = std::false_type;
-    if (pl->c.repel == 1.0) {
-      if (lin) one(T(), T());
-      else one(T(), F());
-    } else {
-      if (lin) one(F(), T());
-      else one(F(), F());
-    }
+    dispatch_body(pl->sched.repel_one, pl->sched.linear, one);
   };
-  for (int G = grouped_lanes(n); G >= 1 && !fits; G /= 2) {
-    switch (G) {
-      case 64: go(std::integral_constant<int, 64>()); break;
-      case 32: go(std::integral_constant<int, 32>()); break;
-      case 16: go(std::integral_constant<int, 16>()); break;
-      case 8: go(std::integral_constant<int, 8>()); break;
-      case 4: go(std::integral_constant<int, 4>()); break;
-      case 2: go(std::integral_constant<int, 2>()); break;
-      default: go(std::integral_constant<int, 1>()); break;
-    }
-  }
-  const char* req = std::getenv("GE_PERSIST_REQUIRE");
-  const bool require = req && *req == '1';
+  for (int G = run.persist_g; G >= 1 && !fits; G /= 2) dispatch_pow2<64>(G, go);
+  const bool require = knobs.persist_require;
   if (!launched) {
     if (require)
       throw Error(GE_ERR_STATE, refused ? "forceAtlas: the cooperative launch was refused"
@@ -2058,33 +1894,18 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
                    const ge_fa_params& p) {
   if (n <= 0 || iterations <= 0) return;
   hipStream_t s = ctx->stream;
-  // One workgroup wins only for tiny levels (n = 14: 3.7 against 12 us per
-  // iteration); from n ~ 100 the multi-block grouped path does (n = 125: 17 us
-  // against 26).  GE_SMALL_MAX moves the bound (tests use it up to kSmallMax).
-  int small_max = kSmallDefault;
-  if (const char* e = std::getenv("GE_SMALL_MAX")) small_max = std::min(kSmallMax, std::atoi(e));
-  // The wide schedule runs the one-workgroup kernel in its general form up to
-  // small_wide_cap(dim) rows (FAST runs the exact kernels there); it has no persistent
-  // kernel: above the bound its long runs replay a graph of fused steps (below).
-  const bool wide = wide_dim(dim);
-  if (wide) small_max = std::min(small_max, small_wide_cap(dim));
-  if (n <= small_max && (p.mode == GE_MODE_STRICT || wide)) {
+  FaRunIn rin{plan_sched_in(n, 0, n, dim, p, device_cus()), nnz, iterations};
+  FaRunSched run = fa_run_schedule(rin);
+  if (run.small) {
     DevBuf<double> dp1(n), fp((size_t)n * dim);
     DevBuf<int> it_state(1);
     hipLaunchKernelGGL(degp1_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, d_ip, d_dx,
                        p.use_weights, dp1.p);
     FaConst c = make_const(p);
-    if (wide) {
-      dispatch_dim(dim, [&](auto Dc) {
-        launch_small_wide<decltype(Dc)::value>(s, n, d_ip, d_ix, d_dx, dp1.p, d_x, fp.p,
-                                               it_state.p, iterations, c);
-      });
-    } else {
-      dispatch_dim_narrow(dim, [&](auto Dc) {
-        constexpr int D = decltype(Dc)::value;
-        launch_small<D>(s, n, nnz, d_ip, d_ix, d_dx, dp1.p, d_x, fp.p, it_state.p, iterations, c);
-      });
-    }
+    dispatch_dim(dim, [&](auto Dc) {
+      launch_small<decltype(Dc)::value>(s, run, rin.plan.wide, n, d_ip, d_ix, d_dx, dp1.p, d_x,
+                                        fp.p, it_state.p, iterations, c);
+    });
     GE_HIP(hipGetLastError());
     GE_HIP(hipStreamSynchronize(s));
     return;
@@ -2101,17 +1922,20 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
   pl.dx = d_dx;
   pl.p = p;
   pl.c = make_const(p);
-  plan_init(&pl);
+  plan_init(&pl, rin.plan);
+  if (!pl.sched_in.masses_ok) {  // the device settled the far field: so does the run
+    rin.plan = pl.sched_in;
+    run = fa_run_schedule(rin);
+  }
   sym_prepare(&pl);  // before any graph capture below
   DevBuf<double> other((size_t)n * dim);
   double* cur = d_x;
   double* nxt = other.p;
   int it = 0;
-  if (p.mode == GE_MODE_STRICT && iterations >= kPersistMin && !wide &&
-      !std::getenv("GE_NO_PERSIST")) {
+  if (run.persist) {
     bool done = false;
     dispatch_dim_narrow(dim, [&](auto Dc) {
-      done = launch_persistent<decltype(Dc)::value>(&pl, d_x, other.p, iterations);
+      done = launch_persistent<decltype(Dc)::value>(&pl, run, d_x, other.p, iterations);
     });
     if (done) {
       if (iterations & 1)
@@ -2120,12 +1944,7 @@ void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix
       return;
     }
   }
-  // Long runs (the coarsest level's 1e5 iterations) replay a captured graph of
-  // kGraphSteps iterations: host launch overhead would otherwise dominate the
-  // microsecond-scale kernels of a small level.
-  constexpr int kGraphSteps = 32;  // even: the buffers are back in place after a replay
-  // (not with the far field: its pass synchronises once, include/ge.h)
-  if (iterations >= 4 * kGraphSteps && !pl.far && !std::getenv("GE_NO_GRAPH")) {
+  if (run.graph) {  // kGraphSteps iterations per replay
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     GE_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -2233,7 +2052,7 @@ int ge_fa_plan_create(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d
     pl->p = *p;
     pl->c = ge::make_const(*p);
     try {
-      ge::plan_init(pl);
+      ge::plan_init(pl, ge::plan_sched_in(n, rb, re, dim, *p, ge::device_cus()));
       // the symmetric path's tables now, not on the first step: that step may run on a
       // caller's stream under graph capture (ge_ctx_set_stream), where sym_prepare's
       // allocations and synchronisation are illegal
@@ -2322,7 +2141,7 @@ int ge_fa_plan_far_info(ge_fa_plan* pl, int* active, int* reason, double* theta,
     GE_REQUIRE(pl, "null plan");
     ge::DeviceGuard g(pl->ctx);
     if (active) *active = pl->far ? 1 : 0;
-    if (reason) *reason = pl->far_reason;
+    if (reason) *reason = pl->sched.far_reason;
     if (pl->far) {
       ge::far_info(pl->far, pl->ctx->stream, theta, item_rows, levels, level_cells, level_points,
                    fallback, accepted, exact_leaves, pair_terms, prep_ms, item_ms);
@@ -2370,6 +2189,29 @@ int ge_fa_plan_kernel_ms(ge_fa_plan* pl, double* rep_ms, double* attr_ms, int* l
     ge::sym_check(pl);
     *rep_ms = pl->events.mean_ms(3, 0, 1, launches);
     *attr_ms = pl->events.mean_ms(3, 1, 2);
+  });
+}
+
+int ge_fa_sched_query(int n, int rb, int re, int dim, const ge_fa_params* p, int cus, int nnz,
+                      int iterations, int masses_ok, int* out) {
+  return ge::guarded([&] {
+    GE_REQUIRE(p && out, "null argument");
+    GE_REQUIRE(n > 0 && dim >= 1 && dim <= ge::kMaxDim, "bad n or dim (dim must be 1..16)");
+    GE_REQUIRE(0 <= rb && rb <= re && re <= n, "bad row range");
+    GE_REQUIRE(cus > 0 && nnz >= 0 && iterations >= 0, "bad cus, nnz or iterations");
+    ge::FaSchedIn in = ge::plan_sched_in(n, rb, re, dim, *p, cus);
+    in.masses_ok = masses_ok != 0;
+    ge::fa_sched_scalars(ge::fa_schedule(in), out);
+    in.rb = 0;  // the run is ge_force_atlas's: the whole level
+    in.re = n;
+    ge::fa_run_scalars(ge::fa_run_schedule({in, nnz, iterations}), out);
+  });
+}
+
+int ge_fa_plan_schedule(ge_fa_plan* pl, int* out) {
+  return ge::guarded([&] {
+    GE_REQUIRE(pl && out, "null argument");
+    ge::fa_sched_scalars(pl->sched, out);
   });
 }
 

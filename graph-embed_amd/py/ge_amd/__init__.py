@@ -93,6 +93,10 @@ _SIGS = {
     "ge_fa_plan_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ge_fa_plan_kernel_ms": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), _ip]),
+    "ge_fa_sched_query": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(FaParams), ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, _ip]),
+    "ge_fa_plan_schedule": (ctypes.c_int, [_vp, _ip]),
     "ge_fa_plan_destroy": (ctypes.c_int, [_vp]),
     "ge_force_atlas_ml": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
                                          _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, ctypes.c_int,
@@ -880,6 +884,46 @@ class FamlPlan:
             pass
 
 
+# GE_FA_STEP_*, GE_FA_REP_* and the scalars GE_FA_SCHED_* of include/ge.h, in index order
+FA_STEPS = ("fused", "stream", "split")
+FA_REPS = ("grouped", "ordered", "ordered_wide", "fast", "sweeps", "farfield")
+FA_SCHED_PLAN_SCALARS = ("mode", "step", "rep", "wide", "lanes", "repel_one", "linear", "per",
+                         "nb", "R", "fast_blocks", "fast_jb", "sym", "far_reason",
+                         "far_item_rows", "fpart")
+FA_SCHED_RUN_SCALARS = ("small", "small_g_domain", "small_g_general", "small_staged",
+                        "small_handover", "persist", "persist_g", "packed", "pack_rows", "graph")
+FA_SCHED_SCALARS = FA_SCHED_PLAN_SCALARS + FA_SCHED_RUN_SCALARS
+FA_SCHED_COUNT = 26  # GE_FA_SCHED_COUNT
+_FA_SCHED_FLAGS = ("wide", "repel_one", "linear", "sym", "fpart", "small", "small_staged",
+                   "persist", "packed", "graph")
+
+
+def _fa_sched_dict(names, values):
+    out = dict(zip(names, (int(v) for v in values)))
+    out["step"] = FA_STEPS[out["step"]]
+    out["rep"] = FA_REPS[out["rep"]]
+    out["far_reason"] = FAR_REASONS[out["far_reason"]]
+    for k in _FA_SCHED_FLAGS:
+        if k in out:
+            out[k] = bool(out[k])
+    return out
+
+
+def fa_schedule(n, dim, cus, rb=0, re=None, iterations=0, nnz=0, masses_ok=True, **params_kw):
+    """The single-level schedule (ge_fa_sched_query; graph-embed_amd/csrc/ge_fa_sched.hpp)
+    with no device touched: which kernels a plan over rows [rb, re) of n vertices runs on
+    a device of `cus` compute units under the knobs now in the environment
+    (FA_SCHED_PLAN_SCALARS), and how ge_force_atlas runs `iterations` of the whole level
+    with nnz CSR entries (FA_SCHED_RUN_SCALARS).  step, rep and far_reason come as the
+    names of FA_STEPS, FA_REPS and FAR_REASONS, mode as MODE_*; masses_ok: the answer of
+    the far field's device check."""
+    out = (ctypes.c_int * FA_SCHED_COUNT)()
+    p = params(**params_kw)
+    _check(lib().ge_fa_sched_query(n, rb, n if re is None else re, dim, ctypes.byref(p), cus, nnz,
+                                   iterations, int(masses_ok), out))
+    return _fa_sched_dict(FA_SCHED_SCALARS, out)
+
+
 class FaPlan:
     """Device-resident ForceAtlas iteration over rows [row_begin, row_end)
     (ge_fa_plan_*).  Device pointers are raw integers (e.g. tensor.data_ptr())."""
@@ -905,6 +949,13 @@ class FaPlan:
         """One repulsion pass alone on the coordinates d_x (n * dim) into d_frep (the
         plan's rows * dim), in the plan's mode (ge_fa_plan_repulse)."""
         _check(lib().ge_fa_plan_repulse(self.h, _vp(d_x), _vp(d_frep)))
+
+    def schedule(self):
+        """The kernels this plan runs (ge_fa_plan_schedule): fa_schedule's
+        FA_SCHED_PLAN_SCALARS as the live plan holds them."""
+        out = (ctypes.c_int * FA_SCHED_COUNT)()
+        _check(lib().ge_fa_plan_schedule(self.h, out))
+        return _fa_sched_dict(FA_SCHED_PLAN_SCALARS, out)
 
     def forces(self, d_out):
         """Copies the forces of the last step or attract ((row_end - row_begin) * dim

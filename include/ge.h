@@ -261,6 +261,59 @@ int ge_fa_plan_far_info(ge_fa_plan* plan, int* active, int* reason, double* thet
  * run without falling back.  Synchronises. */
 int ge_fa_plan_far_layout(ge_fa_plan* plan, int* perm, unsigned long long* keys, double* box,
                           double* cells, double* items);
+/* The single-level schedule (graph-embed_amd/csrc/ge_fa_sched.hpp): which kernels a
+ * plan's step and repulsion pass launch, and how ge_force_atlas runs its iterations.
+ * It changes no result bit.  The GE_* tuning and test knobs of the single level are read
+ * from the environment once, when a plan is created or ge_force_atlas is entered, never
+ * on a step: a plan keeps its route for its lifetime.
+ * ge_fa_sched_query runs the schedule for rows [row_begin, row_end) of n vertices on a
+ * device of `cus` compute units with no context or device touched (it reads the
+ * environment as ge_fa_plan_create does); masses_ok: what the far field's device check
+ * of deg + 1 > 0 would say; nnz and iterations enter the run scalars, which describe
+ * ge_force_atlas on the whole level.  out: GE_FA_SCHED_COUNT ints.
+ * ge_fa_plan_schedule writes the first GE_FA_SCHED_PLAN_COUNT of them, as the live plan
+ * holds them.  The grid scalars hold what their kernel would be launched with on these
+ * rows whether or not STEP / REP select it. */
+#define GE_FA_STEP_FUSED 0  /* fa_grouped_step: n <= grouped_cap(dim) */
+#define GE_FA_STEP_STREAM 1 /* fa_grouped_stream: n <= stream_max */
+#define GE_FA_STEP_SPLIT 2  /* the repulsion pass, then the CSR row kernels */
+#define GE_FA_REP_GROUPED 0      /* fa_repulse_grouped */
+#define GE_FA_REP_ORDERED 1      /* fa_repulse_strict, dim <= 4 */
+#define GE_FA_REP_ORDERED_WIDE 2 /* fa_repulse_strict<D, false, 1>, the wide schedule */
+#define GE_FA_REP_FAST 3         /* fa_repulse_fast + fa_reduce_parts */
+#define GE_FA_REP_SWEEPS 4       /* the symmetric sweeps (ge_sym.hpp) */
+#define GE_FA_REP_FARFIELD 5     /* the far field; FAST's kernels when the box is not finite */
+#define GE_FA_SCHED_MODE 0  /* effective: wide -> STRICT, a FARFIELD that does not run -> FAST */
+#define GE_FA_SCHED_STEP 1  /* ge_fa_plan_step: GE_FA_STEP_* */
+#define GE_FA_SCHED_REP 2   /* the split step's repulsion and ge_fa_plan_repulse: GE_FA_REP_* */
+#define GE_FA_SCHED_WIDE 3
+#define GE_FA_SCHED_LANES 4 /* lanes per row of the fused step / grouped repulsion */
+#define GE_FA_SCHED_REPEL_ONE 5 /* the kernels' body flags (wide: 0, the general bodies) */
+#define GE_FA_SCHED_LINEAR 6
+#define GE_FA_SCHED_PER 7 /* fa_repulse_strict: rows per block, blocks, row slots */
+#define GE_FA_SCHED_NB 8
+#define GE_FA_SCHED_R 9
+#define GE_FA_SCHED_FAST_BLOCKS 10 /* fa_repulse_fast's grid (x, y) */
+#define GE_FA_SCHED_FAST_JB 11
+#define GE_FA_SCHED_SYM 12 /* the plan holds the sweeps' tables */
+#define GE_FA_SCHED_FAR_REASON 13 /* GE_FAR_* */
+#define GE_FA_SCHED_FAR_ITEM_ROWS 14
+#define GE_FA_SCHED_FPART 15 /* FAST's partial sums are allocated */
+#define GE_FA_SCHED_PLAN_COUNT 16
+#define GE_FA_SCHED_SMALL 16 /* ge_force_atlas: every iteration in one workgroup */
+#define GE_FA_SCHED_SMALL_G_DOMAIN 17  /* its domain-only kernel's lanes per row (0: not run) */
+#define GE_FA_SCHED_SMALL_G_GENERAL 18 /* its general kernel's */
+#define GE_FA_SCHED_SMALL_STAGED 19    /* the CSR entries are staged in LDS */
+#define GE_FA_SCHED_SMALL_HANDOVER 20  /* the iteration the domain-only kernel stops at */
+#define GE_FA_SCHED_PERSIST 21   /* the persistent kernel is tried */
+#define GE_FA_SCHED_PERSIST_G 22 /* from this many lanes per row down */
+#define GE_FA_SCHED_PACKED 23    /* at 64 lanes: the packed rows */
+#define GE_FA_SCHED_PACK_ROWS 24 /* 4 or 6 (0: by occupancy) */
+#define GE_FA_SCHED_GRAPH 25     /* the per-iteration path replays a captured graph */
+#define GE_FA_SCHED_COUNT 26
+int ge_fa_sched_query(int n, int row_begin, int row_end, int dim, const ge_fa_params* p, int cus,
+                      int nnz, int iterations, int masses_ok, int* out);
+int ge_fa_plan_schedule(ge_fa_plan* plan, int* out);
 int ge_fa_plan_destroy(ge_fa_plan* plan);
 
 /* ---- layout energy ----

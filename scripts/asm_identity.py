@@ -6,7 +6,8 @@
 
 For every function whose mangled name contains one of the given substrings: the sha256
 of its body in both files (basic-block labels renumbered: they carry the function's
-ordinal in its file) and `identical` or `DIFFERENT`.  --loops prints, per function of
+ordinal in its file, and so does the padding before their comments) and `identical` or
+`DIFFERENT`.  --loops prints, per function of
 NEW.s, the self-looping basic blocks that hold a v_rsq_f64: instructions, fp64
 instructions by opcode and ds_read count (a pair loop's cost per partner).
 Exit status 1 if a function differs or is missing on one side.
@@ -23,7 +24,9 @@ def functions(path, keys):
     for m in re.finditer(r"^(_Z\S*):[^\n]*\n", s, re.M):
         name = m.group(1)
         if any(k in name for k in keys):
-            out[name] = re.sub(r"BB\d+_", "BB_", s[m.end():s.index(".Lfunc_end", m.end())])
+            body = re.sub(r"BB\d+_", "BB_", s[m.end():s.index(".Lfunc_end", m.end())])
+            # a label's comment is padded to a column: the padding follows the ordinal's digits
+            out[name] = re.sub(r"^(\.LBB_\d+:)[ \t]+;", r"\1 ;", body, flags=re.M)
     return out
 
 

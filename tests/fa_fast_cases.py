@@ -104,7 +104,7 @@ PLACES = {257: (3, 256, 70, 137, 128),
 
 
 def chunking(n):
-    """(jb, jchunk) of launch_repulsion_narrow and fa_repulse_fast."""
+    """(jb, jchunk) of fa_schedule (ge_fa_sched.hpp: fast_jb) and fa_repulse_fast."""
     jb = max(1, min(FAST_JBLOCKS, -(-n // TILE_J)))
     return jb, -(-n // jb)
 

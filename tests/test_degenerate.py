@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import fa_route as route
 import ge_amd as ge
 import graphs as G
 
@@ -55,6 +56,7 @@ def test_fa_degenerate(ctx, oracle, monkeypatch, name, small_max):
     A = CASES[name]
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 3, seed=n)
+    assert route.run_kernel(A, 3, 25) == ("fa_small_strict" if small_max == "512" else "fa_grouped_step")
     want = oracle.force_atlas(A, 3, coords=X0, iterations=25)
     got = ctx.force_atlas(A, 3, coords=X0, iterations=25)
     assert np.array_equal(got, want)
@@ -73,6 +75,7 @@ def test_fa_large_level_empty_tiles(ctx, oracle, monkeypatch, segments):
     n = 3000
     for A in (csr(n, []), csr(n, [(7, j) for j in range(n) if j != 7 and j % 2 == 0])):
         X0 = G.random_coords(n, 3, seed=3)
+        assert route.run_kernel(A, 3, 3) == "sweeps+rows"
         want = oracle.force_atlas(A, 3, coords=X0, iterations=3)
         assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=3), want)
 
@@ -105,13 +108,18 @@ HUGE_REPEL = 1e299
     (40, {"GE_SMALL_MAX": "512"}),                         # one workgroup
     (300, {"GE_SMALL_MAX": "0"}),                          # fa_grouped_step
     (4000, {}),                                            # fa_grouped_stream
-    (3000, {"GE_STREAM_MAX": "0", "GE_SMALL_MAX": "0"}),   # fa_repulse_strict + rows
+    # the split step: rows, after the sweeps (a STRICT whole level past stream_max; this
+    # line said fa_repulse_strict until the schedule could be asked)
+    (3000, {"GE_STREAM_MAX": "0", "GE_SMALL_MAX": "0"}),
 ])
 def test_fa_self_pair_overflow(ctx, oracle, monkeypatch, n, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     A = G.rmat(n, 4 * n, seed=n)
     X0 = G.random_coords(n, 3, seed=1)
+    assert route.run_kernel(A, 3, 1, repel=HUGE_REPEL) == {
+        40: "fa_small_strict", 300: "fa_grouped_step", 4000: "fa_grouped_stream",
+        3000: "sweeps+rows"}[n]
     want = oracle.force_atlas(A, 3, coords=X0, iterations=1, repel=HUGE_REPEL)
     got = ctx.force_atlas(A, 3, coords=X0, iterations=1, repel=HUGE_REPEL)
     assert np.isfinite(want).all()

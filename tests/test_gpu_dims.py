@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import dims_cases as D
+import fa_route as route
 import faml_plan as FP
 import ge_amd as ge
 import graphs as G
@@ -39,9 +40,16 @@ def large_cap(d):
     return min(left, 128 * 1024) // (8 * rec_width(d))
 
 
-SMALL_WIDE_CAP = 256  # rows of the one-workgroup kernel above d = 4 (ge_fa.hip small_cap)
+SMALL_WIDE_CAP = 256  # rows of the one-workgroup kernel above d = 4 (ge_fa_sched.hpp small_cap)
 # GE_SMALL_MAX: "512" takes the one-workgroup kernel up to its cap, "0" never
 SMALL = pytest.mark.parametrize("small_max", ["512", "0"], ids=["one-workgroup", "fused"])
+
+
+def small_or_fused(A, d, iterations, small_max, **kw):
+    """The route of a SMALL case below 128 iterations, from the schedule."""
+    n = len(A[0]) - 1
+    want = "fa_small_strict" if small_max == "512" and n <= SMALL_WIDE_CAP else "fa_grouped_step"
+    return route.run_kernel(A, d, iterations, **kw) == want
 
 
 # --------------------------------------------------------------------------
@@ -54,6 +62,7 @@ def test_fa_every_dimension(ctx, oracle, monkeypatch, d, small_max):
     one-workgroup kernel and in the fused step."""
     monkeypatch.setenv("GE_SMALL_MAX", small_max)
     A = G.erdos_renyi(130, 0.06, seed=d)
+    assert small_or_fused(A, d, 3, small_max)
     want = oracle.force_atlas(A, d, iterations=3, seed=d)
     assert np.array_equal(ctx.force_atlas(A, d, iterations=3, seed=d), want)
 
@@ -65,10 +74,13 @@ def test_fa_one_and_two_vertices(ctx, oracle, monkeypatch, d, small_max):
     monkeypatch.setenv("GE_SMALL_MAX", small_max)
     one = (np.array([0, 0], np.int32), np.zeros(0, np.int32), np.zeros(0))
     x1 = G.random_coords(1, d, seed=d)
+    assert small_or_fused(one, d, 7, small_max)
+    assert small_max == "0" or route.schedule(1, d, iterations=7)["small_g_general"] == 8
     assert np.array_equal(ctx.force_atlas(one, d, coords=x1, iterations=7),
                           oracle.force_atlas(one, d, coords=x1, iterations=7))
     two = (np.array([0, 1, 2], np.int32), np.array([1, 0], np.int32), np.ones(2))
     x2 = G.random_coords(2, d, seed=d + 1)
+    assert small_or_fused(two, d, 7, small_max)
     assert np.array_equal(ctx.force_atlas(two, d, coords=x2, iterations=7),
                           oracle.force_atlas(two, d, coords=x2, iterations=7))
 
@@ -77,11 +89,15 @@ def test_fa_one_and_two_vertices(ctx, oracle, monkeypatch, d, small_max):
 @pytest.mark.parametrize("n", [63, 64, 65, SMALL_WIDE_CAP, SMALL_WIDE_CAP + 1])
 @pytest.mark.parametrize("d", D.DIMS)
 def test_fa_one_workgroup_sizes(ctx, oracle, monkeypatch, d, n, small_max):
-    """fa_small_strict<D, G, 256> (general form) around its group sizes -- 2 lanes per row
-    up to 64 rows, one from 65 -- and both sides of its cap of 256 rows, where the fused
-    step takes over; the same sizes on the fused step, one wave per row."""
+    """fa_small_strict<D, G, 256> (general form) with 2 lanes per row (the schedule gives
+    2 from 33 to 128 rows, so 63, 64 and 65 all take them) and one (256), and both sides of
+    its cap of 256 rows, where the fused step takes over; the same sizes on the fused step,
+    one wave per row."""
     monkeypatch.setenv("GE_SMALL_MAX", small_max)
     A = G.erdos_renyi(n, 0.1, seed=n)
+    s = route.schedule(n, d, iterations=30)
+    assert small_or_fused(A, d, 30, small_max)
+    assert s["small_g_general"] == (2 if n <= 128 else 1) if s["small"] else s["lanes"] == 64
     x0 = G.random_coords(n, d, seed=n)
     want = oracle.force_atlas(A, d, coords=x0, iterations=30)
     assert np.array_equal(ctx.force_atlas(A, d, coords=x0, iterations=30), want)
@@ -97,6 +113,7 @@ def test_fa_fixture(ctx, oracle, man, monkeypatch, d, name, small_max):
     monkeypatch.setenv("GE_SMALL_MAX", small_max)
     case = D.fa_case(name, d)
     assert C.input_hashes(case) == man["cases"][f"fa_d{d}"][name]["inputs"]
+    assert small_or_fused(case["A"], d, case["iterations"], small_max, **case["kw"])
     got = C.run_fa(ctx.force_atlas, case)
     assert np.array_equal(got, D.load("fa", d)[name])
     assert np.array_equal(got, C.run_fa(oracle.force_atlas, case))
@@ -107,6 +124,8 @@ def test_fa_long_run_graph_replay(ctx, oracle, d):
     """130 iterations (>= kPersistMin = 128 and >= 4 x 32): no persistent kernel above
     d = 4, so the plan replays the captured graph of 32 fused steps, then 2 plain ones."""
     case = D.fa_case("start_it1", d)
+    assert route.run_kernel(case["A"], d, 130) == "fa_grouped_step"
+    assert route.schedule(D.FA_N, d, iterations=130)["graph"]
     want = oracle.force_atlas(case["A"], d, coords=case["x0"], iterations=130)
     assert np.array_equal(ctx.force_atlas(case["A"], d, coords=case["x0"], iterations=130), want)
 
@@ -120,11 +139,13 @@ def test_fa_ordered_pair_kernel(ctx, man, monkeypatch, d, tiles):
     monkeypatch.setenv("GE_ROWS_TILES", tiles)
     for name in ("start_it25", "repel_2p70", "tiny", "isolated"):
         case = D.fa_case(name, d)
+        assert route.run_kernel(case["A"], d, case["iterations"],
+                                **case["kw"]) == "fa_repulse_strict_wide+rows", name
         assert np.array_equal(C.run_fa(ctx.force_atlas, case), D.load("fa", d)[name]), name
 
 
 def grouped_cap(d):
-    """Records the fused step keeps resident (ge_fa.hip grouped_cap): what 159 KiB leave
+    """Records the fused step keeps resident (ge_fa_sched.hpp grouped_cap): what 159 KiB leave
     after the two term buffers of 256 x d doubles, at most 96 KiB."""
     return min(160 * 1024 - 1024 - 2 * 256 * d * 8, 96 * 1024) // (8 * rec_width(d))
 
@@ -141,6 +162,9 @@ def test_fa_resident_and_streamed_records(ctx, oracle, monkeypatch, d, grp):
         A = G.rmat(n, 5 * n, seed=n)  # isolated vertices included
         x0 = G.random_coords(n, d, seed=d)
         x0[n // 2, d - 1] = C.TINY  # one tile outside the exact-division domain
+        assert route.run_kernel(A, d, 2) == (
+            "fa_grouped_step" if n == grouped_cap(d) else "fa_grouped_stream"), n
+        assert route.schedule(n, d)["lanes"] == (8 if grp else 64)
         want = oracle.force_atlas(A, d, coords=x0, iterations=2)
         assert np.array_equal(ctx.force_atlas(A, d, coords=x0, iterations=2), want), n
 
@@ -150,6 +174,8 @@ def test_fa_group_size_threshold(ctx, oracle):
     for n in (8191, 8192):
         A = G.rmat(n, 4 * n, seed=7)
         x0 = G.random_coords(n, 5, seed=3)
+        assert route.run_kernel(A, 5, 1) == "fa_grouped_stream"
+        assert route.schedule(n, 5)["lanes"] == (64 if n == 8191 else 8)
         want = oracle.force_atlas(A, 5, coords=x0, iterations=1)
         assert np.array_equal(ctx.force_atlas(A, 5, coords=x0, iterations=1), want), n
 
@@ -166,6 +192,8 @@ def test_fa_plan_row_shard(ctx, oracle, monkeypatch, d, stream_max):
     case = D.fa_case("start_it1", d)
     A, x0 = C.symmetric_weights(case["A"]), case["x0"]
     n = D.FA_N
+    assert route.step_kernel(n, d, rb=rb, re=re) == (
+        "fa_grouped_step" if stream_max is None else "fa_repulse_strict_wide+rows")
     dev = torch.device("cuda:0")
     t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in A]
     x = torch.from_numpy(x0.copy()).to(dev)
@@ -205,6 +233,7 @@ def test_fa_heavy_rows(ctx, oracle, monkeypatch, d, segments):
     assert list(deg[[7, 8, 9, 300]]) == [511, 512, 513, 1100] and (deg == 0).any()
     A = C.symmetric_weights(A)
     x0 = G.random_coords(1500, d, seed=d)
+    assert route.run_kernel(A, d, 3) == "fa_repulse_strict_wide+rows"
     want = oracle.force_atlas(A, d, coords=x0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, d, coords=x0, iterations=3), want)
 
@@ -218,6 +247,7 @@ def test_fa_classed_heavy_row(ctx, oracle, monkeypatch, d):
     A = G.with_hubs(G.rmat(2600, 9000, seed=d), [(5, 2300)], seed=d)
     assert np.diff(A[0]).max() > 2048
     x0 = G.random_coords(2600, d, seed=d)
+    assert route.run_kernel(A, d, 2) == "fa_repulse_strict_wide+rows"
     want = oracle.force_atlas(A, d, coords=x0, iterations=2)
     assert np.array_equal(ctx.force_atlas(A, d, coords=x0, iterations=2), want)
 
@@ -248,6 +278,8 @@ def test_fa_overflowing_repel(ctx, oracle, d):
 def test_fa_fast_mode_runs_the_exact_kernels(ctx, oracle):
     """GE_MODE_FAST has no kernels above d = 4: it returns the STRICT bits."""
     case = D.fa_case("start_it2", 8)
+    assert route.schedule(D.FA_N, 8, mode=ge.MODE_FAST)["mode"] == ge.MODE_STRICT
+    assert route.run_kernel(case["A"], 8, 2, mode=ge.MODE_FAST) == "fa_grouped_step"
     got = ctx.force_atlas(case["A"], 8, coords=case["x0"], iterations=2, mode=ge.MODE_FAST)
     assert np.array_equal(got, D.load("fa", 8)["start_it2"])
 
@@ -428,6 +460,8 @@ def test_wide_one_workgroup_reproduces_reference_fixtures(ctx, golden, monkeypat
     monkeypatch.setenv("GE_SMALL_MAX", "512")
     case = C.fa_case(name)
     assert len(case["A"][0]) - 1 <= SMALL_WIDE_CAP
+    assert route.run_kernel(case["A"], case["dim"], case["iterations"], **case["kw"]) == "fa_small_strict"
+    assert route.schedule(97, case["dim"])["wide"]
     assert np.array_equal(C.run_fa(ctx.force_atlas, case), golden("ref_" + name)["x"])
 
 
@@ -451,6 +485,8 @@ def test_wide_schedule_equals_default_at_d4(ctx, monkeypatch, stream_max):
     x0 = G.random_coords(1300, 4, seed=1)
     want = ctx.force_atlas(A, 4, coords=x0, iterations=5)
     monkeypatch.setenv("GE_WIDE_MIN_DIM", "4")
+    assert route.schedule(1300, 4)["wide"] and route.run_kernel(A, 4, 5) == (
+        "fa_grouped_step" if stream_max is None else "fa_repulse_strict_wide+rows")
     assert np.array_equal(ctx.force_atlas(A, 4, coords=x0, iterations=5), want)
 
 

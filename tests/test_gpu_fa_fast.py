@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import fa_fast_cases as C
+import fa_route as route
 import ge_amd as ge
 from faml_fast_cases import REL_TOL_FAST
 
@@ -113,6 +114,8 @@ def test_force_bound(ctx, n, variant, dim, repel, use_weights):
     X = C.coords(n, dim, variant)
     Fr, T = C.reference(n, variant, dim, repel, use_weights)
     x = dv.up(X)
+    assert route.repulse_kernel(n, dim, mode=ge.MODE_FAST, repel=repel,
+                                use_weights=use_weights) == "fa_repulse_fast"
     for name, mode in (("FAST", ge.MODE_FAST), ("STRICT", ge.MODE_STRICT)):
         plan = dv.plan(dim, mode=mode, repel=repel, use_weights=use_weights)
         try:
@@ -155,6 +158,8 @@ def test_row_shards_equal_the_whole_plan(ctx, n, d):
     out = dv.torch.full((n + GUARD, d), SENTINEL, dtype=dv.torch.float64, device=dv.dev)
     done = np.zeros(n, bool)
     for rb, re in _shards(n):
+        assert route.repulse_kernel(n, d, rb=rb, re=re, mode=ge.MODE_FAST,
+                                    repel=3.5) == "fa_repulse_fast"
         p = dv.plan(d, rb, re, mode=ge.MODE_FAST, repel=3.5)
         try:
             dv.repulse(p, x, rb, re, out=out)
@@ -178,6 +183,7 @@ def test_step_is_fast_repulsion_plus_strict_rows(ctx, monkeypatch, n, d):
     x = dv.up(C.coords(n, d))
     y, y2, f = t.full_like(x, SENTINEL), t.full_like(x, SENTINEL), t.full_like(x, SENTINEL)
     kw = dict(repel=3.5, use_weights=1)
+    assert route.step_kernel(n, d, mode=ge.MODE_FAST, **kw) == "fa_repulse_fast+rows"
     stepper = dv.plan(d, mode=ge.MODE_FAST, **kw)
     repulser = dv.plan(d, mode=ge.MODE_FAST, **kw)
     monkeypatch.setenv("GE_FA_SYM", "0")  # no sweep tables on the STRICT plan
@@ -223,14 +229,18 @@ def test_force_atlas_equals_hand_stepped_plan(ctx, monkeypatch):
     for iterations in (2, 130):
         want = _hand_stepped(ctx, n, d, X, iterations)
         assert np.isfinite(want).all()
+        assert route.run_kernel(A, d, iterations, mode=ge.MODE_FAST) == "fa_repulse_fast+rows"
+        assert route.schedule(n, d, iterations=iterations, mode=ge.MODE_FAST)["graph"] == (iterations == 130)
         got = ctx.force_atlas(A, d, coords=X, iterations=iterations, mode=ge.MODE_FAST)
         assert got.tobytes() == want.tobytes(), iterations
     monkeypatch.setenv("GE_NO_GRAPH", "1")
+    assert not route.schedule(n, d, iterations=130, mode=ge.MODE_FAST)["graph"]
     got = ctx.force_atlas(A, d, coords=X, iterations=130, mode=ge.MODE_FAST)
     assert got.tobytes() == want.tobytes()
     monkeypatch.delenv("GE_NO_GRAPH")
     n, d = 5, 2
     A, X = C.case(n)[0], C.coords(n, d)
+    assert route.run_kernel(A, d, 3, mode=ge.MODE_FAST) == "fa_repulse_fast+rows"
     got = ctx.force_atlas(A, d, coords=X, iterations=3, mode=ge.MODE_FAST)
     assert got.tobytes() == _hand_stepped(ctx, n, d, X, 3).tobytes()
     strict = ctx.force_atlas(A, d, coords=X, iterations=3)

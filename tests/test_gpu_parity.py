@@ -5,6 +5,7 @@ mode must stay within the north star's 1e-5 relative bar.
 import numpy as np
 import pytest
 
+import fa_route as route
 import ge_amd as ge
 import graphs as G
 from faml_plan import assert_census, run_plan
@@ -36,6 +37,7 @@ def test_fa_golden_supplied_init(ctx, golden, monkeypatch, small_max):
     monkeypatch.setenv("GE_SMALL_MAX", small_max)
     g = golden("fa_er300_d3")
     A = (g["A_ip"], g["A_ix"], g["A_dx"])
+    assert route.run_kernel(A, 3, 100) == ("fa_small_strict" if small_max == "512" else "fa_grouped_step")
     for it in (1, 10, 100):
         X = ctx.force_atlas(A, 3, coords=g["x0"], iterations=it)
         assert np.array_equal(X, g[f"x_it{it}"]), it
@@ -53,6 +55,7 @@ def test_fa_small_kernel_dims(ctx, oracle, monkeypatch, dim):
     monkeypatch.setenv("GE_SMALL_MAX", "512")
     A = G.erdos_renyi(97, 0.06, seed=dim)
     X0 = G.random_coords(97, dim, seed=dim)
+    assert route.run_kernel(A, dim, 30) == "fa_small_strict"
     want = oracle.force_atlas(A, dim, coords=X0, iterations=30)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=30), want)
 
@@ -62,6 +65,7 @@ def test_fa_tiled_kernel_bitexact(ctx, oracle, n, dim):
     A = G.rmat(n, 8 * n, seed=n)  # isolated vertices included (gravity only)
     m = len(A[0]) - 1
     assert m > 1024  # the multi-block (plan) path, not the one-workgroup path
+    assert route.run_kernel(A, dim, 5) == "fa_grouped_step"
     X0 = G.random_coords(m, dim, seed=1)
     want = oracle.force_atlas(A, dim, coords=X0, iterations=5)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=5), want)
@@ -79,6 +83,7 @@ def test_fa_degree_classes(ctx, oracle, monkeypatch, use_weights, tiles):
     A = (A[0], A[1], np.random.RandomState(2).uniform(0.5, 2.0, len(A[1])))
     deg = np.diff(A[0])
     assert deg.max() > 4096 and ((deg > 32) & (deg <= 2048)).any()
+    assert route.run_kernel(A, 3, 4, use_weights=use_weights) == "sweeps+rows"
     X0 = G.random_coords(len(deg), 3, seed=4)
     want = oracle.force_atlas(A, 3, coords=X0, iterations=4, use_weights=use_weights)
     got = ctx.force_atlas(A, 3, coords=X0, iterations=4, use_weights=use_weights)
@@ -101,6 +106,7 @@ def test_fa_row_tiles(ctx, oracle, monkeypatch, dim, segments):
     deg = np.diff(A[0])
     assert list(deg[[7, 8, 9, 300]]) == [1023, 1024, 1025, 700] and (deg == 0).any()
     assert list(deg[[2000, 2001, 2002]]) == [511, 512, 513]
+    assert route.run_kernel(A, dim, 3) == "sweeps+rows"
     X0 = G.random_coords(len(deg), dim, seed=dim)
     want = oracle.force_atlas(A, dim, coords=X0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=3), want)
@@ -118,6 +124,7 @@ def test_fa_heavy_segments_binade_and_fallback(ctx, oracle, monkeypatch, scale):
     A = G.with_degrees(G.rmat(7000, 28000, seed=4), {3: 5000, 11: 2600, 12: 513}, seed=5)
     A = (A[0], A[1], A[2] * scale)
     X0 = G.random_coords(7000, 3, seed=9)
+    assert route.run_kernel(A, 3, 3) == "sweeps+rows"
     for it in (1, 3):
         want = oracle.force_atlas(A, 3, coords=X0, iterations=it)
         got = ctx.force_atlas(A, 3, coords=X0, iterations=it)
@@ -131,6 +138,8 @@ def test_fa_row_tiles_graph_replay(ctx, oracle, monkeypatch):
     monkeypatch.setenv("GE_ROWS_TILES", "1")
     A = G.with_degrees(G.rmat(3300, 12000, seed=21), {5: 1500, 6: 900}, seed=2)
     X0 = G.random_coords(3300, 2, seed=6)
+    assert route.run_kernel(A, 2, 130) == "sweeps+rows"  # past grouped_cap: no persistent kernel
+    assert route.schedule(3300, 2, iterations=130)["graph"]
     want = oracle.force_atlas(A, 2, coords=X0, iterations=130)
     assert np.array_equal(ctx.force_atlas(A, 2, coords=X0, iterations=130), want)
 
@@ -145,6 +154,7 @@ def test_fa_repulsion_row_slots(ctx, oracle, monkeypatch, R):
     A = G.rmat(9000, 60000, seed=3)
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 3, seed=8)
+    assert route.run_kernel(A, 3, 3) == "fa_repulse_strict+rows" and route.schedule(n, 3)["R"] == int(R)
     want = oracle.force_atlas(A, 3, coords=X0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=3), want)
 
@@ -161,6 +171,9 @@ def test_fa_repulsion_full_row_slots(ctx, oracle, monkeypatch, R):
     A = G.rmat(9000, 60000, seed=5)
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 3, seed=9)
+    s = route.schedule(n, 3)
+    assert route.run_kernel(A, 3, 3) == "fa_repulse_strict+rows"
+    assert (s["R"], s["per"], s["nb"]) == (int(R), 4544, 2)
     want = oracle.force_atlas(A, 3, coords=X0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=3), want)
 
@@ -171,14 +184,16 @@ def test_fa_repulsion_full_row_slots(ctx, oracle, monkeypatch, R):
 def test_fa_symmetric_repulsion(ctx, oracle, monkeypatch, n, dim, repel):
     """Single-level forceAtlas with the symmetric sweeps (ge_sym.hpp): the level as
     one aggregate of ceil(n / 64) row tiles, each unordered pair evaluated once,
-    column sums handed from sweep to sweep; ragged last tile, one and two tiles,
+    column sums handed from sweep to sweep; ragged last tile, two tiles,
     every dimension, repel != 1 and a repel large enough (1e21) to leave the
-    shared-reciprocal domain (the `/` forms)."""
+    shared-reciprocal domain (the `/` forms).  (n = 64, meant as the one-tile case, is
+    within GE_SMALL_MAX's default and has always been taken by the one-workgroup run.)"""
     monkeypatch.setenv("GE_STREAM_MAX", "0")
     monkeypatch.setenv("GE_FA_SYM", "1")
     A = G.rmat(n, 6 * n, seed=n + dim)
     m = len(A[0]) - 1
     X0 = G.random_coords(m, dim, seed=dim)
+    assert route.run_kernel(A, dim, 3, repel=repel) == ("sweeps+rows" if m > 64 else "fa_small_strict")
     want = oracle.force_atlas(A, dim, coords=X0, iterations=3, repel=repel)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=3, repel=repel), want)
 
@@ -186,13 +201,18 @@ def test_fa_symmetric_repulsion(ctx, oracle, monkeypatch, n, dim, repel):
 def test_fa_symmetric_repulsion_domain_and_ties(ctx, oracle, monkeypatch):
     """Symmetric sweeps with a coordinate outside the exact-division domain (its
     tiles take the `/` forms), coincident points (distance clamped to eps) and
-    isolated vertices, over enough iterations to replay a captured graph."""
+    isolated vertices.  (Its 130 iterations were meant to replay a captured graph of
+    sweeps; at n <= grouped_cap a STRICT run of 128 iterations or more is the persistent
+    kernel's whatever GE_STREAM_MAX and GE_FA_SYM say, and that is what has always run
+    here.  Sweeps under graph replay: test_fa_row_tiles_graph_replay.)"""
     monkeypatch.setenv("GE_STREAM_MAX", "0")
     monkeypatch.setenv("GE_FA_SYM", "1")
     A = G.rmat(3000, 12000, seed=44)
     X0 = G.random_coords(3000, 3, seed=8)
     X0[1500, 1] = 1e-70
     X0[10] = X0[11]
+    assert route.run_kernel(A, 3, 130) == "fa_grouped_persistent"
+    assert route.repulse_kernel(3000, 3) == "sweeps"
     want = oracle.force_atlas(A, 3, coords=X0, iterations=130)
     assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=130), want)
 
@@ -208,6 +228,10 @@ def test_fa_small_kernel_handover(ctx, oracle, monkeypatch, hook):
     A = G.largest_component(G.rmat(300, 1500, seed=12))
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 3, seed=3)
+    s = route.schedule(n, 3, iterations=80, nnz=len(A[1]))
+    assert route.run_kernel(A, 3, 80) == "fa_small_strict"
+    assert (s["small_g_domain"] == 0) == (hook[0] == "GE_SMALL_GENERAL_ONLY")
+    assert s["small_handover"] == (80 if hook[0] == "GE_SMALL_GENERAL_ONLY" else int(hook[1]))
     want = oracle.force_atlas(A, 3, coords=X0, iterations=80)
     assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=80), want)
 
@@ -221,6 +245,7 @@ def test_fa_small_kernel_out_of_domain_start(ctx, oracle, monkeypatch, small_max
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 2, seed=4)
     X0[3, 1] = 1e-70
+    assert route.run_kernel(A, 2, 25) == ("fa_small_strict" if small_max == "512" else "fa_grouped_step")
     want = oracle.force_atlas(A, 2, coords=X0, iterations=25)
     assert np.array_equal(ctx.force_atlas(A, 2, coords=X0, iterations=25), want)
 
@@ -236,6 +261,8 @@ def test_fa_grouped_repulsion(ctx, oracle, monkeypatch, grp, n, dim, split):
         monkeypatch.setenv("GE_GRP_SPLIT", "1")
     A = G.rmat(n, 6 * n, seed=n)
     X0 = G.random_coords(n, dim, seed=int(grp))
+    assert route.run_kernel(A, dim, 4) == ("fa_repulse_grouped+rows" if split == "1" else "fa_grouped_step")
+    assert route.schedule(n, dim)["lanes"] == int(grp)
     want = oracle.force_atlas(A, dim, coords=X0, iterations=4)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=4), want)
 
@@ -252,15 +279,23 @@ def test_fa_grouped_stream(ctx, oracle, monkeypatch, grp, n, dim):
     A = G.with_degrees(G.rmat(n, 5 * n, seed=n), {17: 700}, seed=1)
     X0 = G.random_coords(n, dim, seed=int(grp) + 1)
     X0[2500, 0] = 1e-70
+    assert route.run_kernel(A, dim, 3) == "fa_grouped_stream"
+    assert grp == "0" or route.schedule(n, dim)["lanes"] == int(grp)
     want = oracle.force_atlas(A, dim, coords=X0, iterations=3)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=3), want)
 
 
 def test_fa_small_level_graph_replay(ctx, oracle):
-    """n = 127-ish coarsest level (fused grouped kernel, 64 lanes per row) over
-    3000 iterations: captured-graph replay of the fused step, bit-exact."""
+    """n = 127-ish coarsest level (64 lanes per row) over 3000 iterations, bit-exact.
+    (Written for the captured-graph replay of the fused step; since the persistent kernel
+    exists a STRICT run of this size and length tries that first, and falls back to the
+    replay only where its grid does not fit.  The replay itself:
+    test_fa_persistent_matches_graph_replay_long.)"""
     A = G.largest_component(G.rmat(160, 700, seed=9))
     assert 64 < len(A[0]) - 1 <= 3072
+    assert route.run_kernel(A, 3, 3000) == "fa_grouped_persistent"
+    s = route.schedule(len(A[0]) - 1, 3, iterations=3000)
+    assert (s["step"], s["lanes"], s["graph"]) == ("fused", 64, True)  # the fall-back
     want = oracle.force_atlas(A, 3, iterations=3000, seed=77)
     assert np.array_equal(ctx.force_atlas(A, 3, iterations=3000, seed=77), want)
 
@@ -288,6 +323,10 @@ def test_fa_persistent_small_level(ctx, oracle, monkeypatch, n, dim, grp, its):
         monkeypatch.setenv("GE_GRP_G", grp)
     A = G.rmat(n, 6 * n, seed=n + dim)
     X0 = G.random_coords(n, dim, seed=n)
+    s = route.schedule(n, dim, iterations=its)
+    assert route.run_kernel(A, dim, its) == "fa_grouped_persistent"
+    assert s["packed"] == (grp != "nopack") and s["pack_rows"] == (int(grp[4:]) if grp[:4] == "pack" else 0)
+    assert s["persist_g"] == (int(grp) if grp.isdigit() and grp != "0" else s["lanes"])
     want = oracle.force_atlas(A, dim, coords=X0, iterations=its)
     assert np.array_equal(ctx.force_atlas(A, dim, coords=X0, iterations=its), want)
 
@@ -306,6 +345,7 @@ def test_fa_persistent_params_and_domain(ctx, oracle, monkeypatch, pack):
     n = len(A[0]) - 1
     X0 = G.random_coords(n, 3, seed=5)
     kw = dict(ks=0.2, ksmax=2.0, repel=1.5, attract=0.7, gravity=2.0, use_weights=0)
+    assert route.run_kernel(A, 3, 150, **kw) == route.run_kernel(A, 3, 130) == "fa_grouped_persistent"
     want = oracle.force_atlas(A, 3, coords=X0, iterations=150, **kw)
     assert np.array_equal(ctx.force_atlas(A, 3, coords=X0, iterations=150, **kw), want)
     X0[7, 2] = 1e-70
@@ -322,8 +362,11 @@ def test_fa_persistent_matches_graph_replay_long(ctx, monkeypatch):
     assert 900 < n <= 3072
     X0 = G.random_coords(n, 3, seed=12)
     monkeypatch.setenv("GE_PERSIST_REQUIRE", "1")
+    assert route.run_kernel(A, 3, 20000) == "fa_grouped_persistent"
     got = ctx.force_atlas(A, 3, coords=X0, iterations=20000)
     monkeypatch.setenv("GE_NO_PERSIST", "1")
+    assert route.run_kernel(A, 3, 20000) == "fa_grouped_step"
+    assert route.schedule(n, 3, iterations=20000)["graph"]
     assert np.array_equal(got, ctx.force_atlas(A, 3, coords=X0, iterations=20000))
 
 
@@ -331,6 +374,7 @@ def test_fa_coarsest_level_1e5_iterations(ctx, oracle):
     # the coarsest level runs the default 100000 iterations (src/embed.cpp:586);
     # chaos amplifies any op-order difference far beyond 1e-5 over that horizon
     A = G.largest_component(G.rmat(40, 120, seed=3))
+    assert route.run_kernel(A, 3, 100000) == "fa_small_strict"
     want = oracle.force_atlas(A, 3, iterations=100000, seed=555)
     got = ctx.force_atlas(A, 3, iterations=100000, seed=555)
     assert np.array_equal(got, want)
@@ -352,6 +396,7 @@ def test_fa_coarsest_level_production_horizon(ctx, golden, monkeypatch, grp):
         monkeypatch.setenv("GE_GRP_G", grp)
     g = golden("fa_coarsest_1e5")
     A = (g["A_ip"], g["A_ix"], g["A_dx"])
+    assert route.run_kernel(A, 3, int(g["iterations"])) == "fa_grouped_persistent"
     X = ctx.force_atlas(A, 3, iterations=int(g["iterations"]), seed=int(g["seed"]))
     assert np.array_equal(X, g["x"])
 
@@ -366,6 +411,7 @@ def test_fa_coarsest_level_shared_device(golden):
     g = golden("fa_coarsest_1e5")
     A = (g["A_ip"], g["A_ix"], g["A_dx"])
     its, seed = int(g["iterations"]), int(g["seed"])
+    assert route.run_kernel(A, 3, its) == "fa_grouped_persistent"
     ctxs = [ge.Context(0) for _ in range(3)]
     out, errs = [None] * 3, []
 
@@ -424,8 +470,8 @@ def test_fa_fast_mode_tolerance(ctx, oracle):
 def test_fa_plan_row_shards_compose(ctx, oracle, monkeypatch, path):
     """Two row shards stepping over a shared coordinate array (what each rank of
     the multi-GPU path runs between all-gathers) equal the unsharded iteration:
-    small-level fused kernel, or the large-level kernels (repulsion row slots,
-    row tiles, heavy-row segments inside a shard)."""
+    small-level fused kernel, or the split step (at this size the grouped repulsion,
+    then row tiles and heavy-row segments inside a shard)."""
     torch = pytest.importorskip("torch")
     if path == "rows":
         monkeypatch.setenv("GE_STREAM_MAX", "0")
@@ -441,6 +487,9 @@ def test_fa_plan_row_shards_compose(ctx, oracle, monkeypatch, path):
     x = torch.from_numpy(X0.copy()).to(dev)
     y = torch.empty_like(x)
     half = n // 2
+    for lo, hi in ((0, half), (half, n)):
+        assert route.step_kernel(n, 3, rb=lo, re=hi) == (
+            "fa_grouped_step" if path == "fused" else "fa_repulse_grouped+rows")
     plans = [ctx.fa_plan(n, len(A[1]), ip.data_ptr(), ix.data_ptr(), dx.data_ptr(), 3, lo, hi)
              for lo, hi in ((0, half), (half, n))]
     for _ in range(6):
