@@ -47,6 +47,7 @@
 #include "ge_energy.hpp"
 #include "ge_fa_sched.hpp"
 #include "ge_far.hpp"
+#include "ge_group.hpp"
 #include "ge_internal.hpp"
 #include "ge_pair.hpp"
 #include "ge_rows.hpp"
@@ -422,44 +423,7 @@ struct FaRows {
 
 // (kSmallMax, small_cap and the other bounds of these kernels: ge_fa_sched.hpp)
 
-// The G lanes of a group hold U terms each (term u of lane g is partner
-// g + G*u of the chunk); the group's first lane adds the first cnt in order.
-template <int D, int G, int U>
-__device__ __forceinline__ void group_add(const double (&t)[U][D], int tid, int g, int cnt,
-                                          bool leader, double* __restrict__ tb,
-                                          double (&acc)[D]) {
-  if (G == 1) {
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (u < cnt)
-#pragma unroll
-        for (int k = 0; k < D; ++k) acc[k] = acc[k] + t[u][k];
-    return;
-  }
-  const int base = tid - g;  // the group's first lane
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-#pragma unroll
-    for (int k = 0; k < D; ++k) tb[(base * U + g + G * u) * D + k] = t[u][k];
-  wave_lds_sync();
-  if (leader) {
-    constexpr int B = (G * U < 8) ? G * U : 8;  // terms read ahead of the ordered adds
-#pragma unroll
-    for (int l0 = 0; l0 < G * U; l0 += B) {
-      double v[B][D];
-#pragma unroll
-      for (int l = 0; l < B; ++l)
-#pragma unroll
-        for (int k = 0; k < D; ++k) v[l][k] = tb[(base * U + l0 + l) * D + k];
-#pragma unroll
-      for (int l = 0; l < B; ++l)
-        if (l0 + l < cnt)
-#pragma unroll
-          for (int k = 0; k < D; ++k) acc[k] = acc[k] + v[l][k];
-    }
-  }
-  wave_lds_sync();
-}
+// (group_add, the ordered sum of a group's terms by its first lane: ge_group.hpp)
 
 // a += p[0] + ... + p[cnt-1] in order for a chunk of G slots (p 16-byte
 // aligned; slots >= cnt are added as +0.0, which leaves a unchanged: a running
@@ -1887,6 +1851,13 @@ bool launch_persistent(ge_fa_plan* pl, const FaRunSched& run, double* Xa, double
     return false;
   }
   return true;
+}
+
+void launch_degp1(hipStream_t s, int n, const int* d_ip, const double* d_dx, int use_weights,
+                  double* d_dp1) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(degp1_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, d_ip, d_dx,
+                     use_weights, d_dp1);
 }
 
 void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix,

@@ -324,6 +324,81 @@ inline FaRunSched fa_run_schedule(const FaRunIn& in) {
   return r;
 }
 
+// ge_force_atlas_batch: many independent graphs in one call (ge_fa_batch.hip).  A graph of
+// n rows and `entries` stored entries runs in one of three classes; none changes a bit:
+//   wave    1 <= n <= kBatchWaveMax, STRICT or the wide schedule: one wave per graph,
+//           kBatchWaves graphs per workgroup of one launch; lanes per row: the largest
+//           power of two with n lanes <= 64 (GE_SMALL_G where it fits the wave);
+//   block   up to small_cap(dim) rows, same modes: one workgroup per graph of one launch,
+//           fa_small_strict's general form; lanes per row from small_group, at most
+//           kBatchBlockLanes (more lanes would need n <= 64);
+//   serial  everything else -- larger graphs, and every graph of a narrow dimension under
+//           FAST / FARFIELD, where ge_force_atlas itself leaves the one-workgroup kernel:
+//           fa_run_device, one graph after another.  An empty graph is serial and runs
+//           nothing.
+// Within a class the graphs launch by descending n + entries (fa_batch_order), so the
+// waves of a workgroup finish together and the largest workgroups start first.
+constexpr int kBatchWaveMax = 64;
+constexpr int kBatchWaves = 4;
+constexpr int kBatchBlockLanes = 4;
+
+struct FaBatchIn {
+  int dim = 0;
+  int mode = GE_MODE_STRICT;  // as requested (ge_fa_params.mode)
+  bool wide = false;          // the wide schedule (wide_dim, ge_pair.hpp)
+  FaKnobs knobs;
+};
+
+// threads of the block class's workgroup: fa_small_strict's general kernel's
+inline int fa_batch_block_threads(const FaBatchIn& in) {
+  return in.wide || in.dim > kNarrowMaxDim ? kSmallWideT : kSmallGenT;
+}
+
+inline void fa_batch_class(const FaBatchIn& in, int n, int* cls, int* lanes) {
+  const bool wide = in.wide || in.dim > kNarrowMaxDim;
+  const bool one_workgroup = in.mode == GE_MODE_STRICT || wide;  // as FaRunSched::small
+  const int cap = wide ? small_wide_cap(in.dim) : small_cap(in.dim);
+  *cls = GE_FA_BATCH_SERIAL;
+  *lanes = 0;
+  if (!one_workgroup || n < 1 || n > cap) return;
+  if (n <= kBatchWaveMax) {
+    int G = 1;
+    while (n * G * 2 <= 64) G *= 2;
+    if (in.knobs.small_g && n * in.knobs.small_g <= 64) G = in.knobs.small_g;  // tuning override
+    *cls = GE_FA_BATCH_WAVE;
+    *lanes = G;
+    return;
+  }
+  *cls = GE_FA_BATCH_BLOCK;
+  *lanes = std::min(kBatchBlockLanes, fa_sched::small_group(n, fa_batch_block_threads(in), in.knobs));
+}
+
+// Classes and lanes per row of `count` graphs (cls, lanes: count ints each) and
+// totals[GE_FA_BATCH_TOTALS] = {waves, blocks, serials, workgroups of the wave launch}.
+inline void fa_batch_schedule(const FaBatchIn& in, int count, const int* sizes, int* cls,
+                              int* lanes, int* totals) {
+  int per[3] = {0, 0, 0};
+  for (int g = 0; g < count; ++g) {
+    fa_batch_class(in, sizes[g], &cls[g], &lanes[g]);
+    ++per[cls[g]];
+  }
+  totals[0] = per[GE_FA_BATCH_WAVE];
+  totals[1] = per[GE_FA_BATCH_BLOCK];
+  totals[2] = per[GE_FA_BATCH_SERIAL];
+  totals[3] = (per[GE_FA_BATCH_WAVE] + kBatchWaves - 1) / kBatchWaves;
+}
+
+// The graphs of class c in launch order: descending n + entries, ties by index.
+inline void fa_batch_order(int count, const int* sizes, const int* entries, const int* cls, int c,
+                           int* out) {
+  int k = 0;
+  for (int g = 0; g < count; ++g)
+    if (cls[g] == c) out[k++] = g;
+  std::stable_sort(out, out + k, [&](int a, int b) {
+    return (long long)sizes[a] + entries[a] > (long long)sizes[b] + entries[b];
+  });
+}
+
 // The scalars of ge_fa_sched_query / ge_fa_plan_schedule (GE_FA_SCHED_*).
 inline void fa_sched_scalars(const FaSched& s, int* out) {
   out[GE_FA_SCHED_MODE] = s.mode;

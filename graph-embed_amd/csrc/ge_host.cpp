@@ -256,6 +256,102 @@ void fa_host(ge_ctx* ctx, int n, const int* ip, const int* ix, const double* dx,
 }
 
 // ---------------------------------------------------------------------------
+// many graphs in one call (ge_force_atlas_batch): fa_host per graph around one
+// fa_batch_device
+
+namespace {
+
+std::string graph_msg(int g, const char* what) {
+  return "graph " + std::to_string(g) + ": " + what;
+}
+
+// The block-diagonal CSR of ge_force_atlas_batch: offsets ascending from 0, indptr as
+// check_csr, every column inside its graph's block.  Messages name the graph.
+void check_batch(int count, const int* off, const int* ip, const int* ix, const double* dx) {
+  GE_REQUIRE(count >= 0, "negative graph count");
+  if (count == 0) return;
+  GE_REQUIRE(off, "null offsets");
+  GE_REQUIRE(off[0] == 0, graph_msg(0, "the offsets do not ascend from 0"));
+  for (int g = 0; g < count; ++g)
+    GE_REQUIRE(off[g + 1] >= off[g], graph_msg(g, "the offsets do not ascend from 0"));
+  if (off[count] == 0) return;
+  GE_REQUIRE(ip && ix && dx, "null CSR array");
+  GE_REQUIRE(ip[0] == 0, graph_msg(0, "bad indptr"));
+  for (int g = 0; g < count; ++g) {
+    const int r0 = off[g], r1 = off[g + 1];
+    for (int i = r0; i < r1; ++i) GE_REQUIRE(ip[i + 1] >= ip[i], graph_msg(g, "indptr decreases"));
+    long long bad = 0;
+    for (int e = ip[r0]; e < ip[r1]; ++e) bad += ix[e] < r0 || ix[e] >= r1;
+    GE_REQUIRE(bad == 0, graph_msg(g, "an entry's column lies outside the graph's block"));
+  }
+}
+
+void fa_batch_host(ge_ctx* ctx, int count, const int* off, const int* ip, const int* ix,
+                   const double* dx, int dim, double* X, bool init_random, const unsigned* seeds,
+                   int iterations, const ge_fa_params& p) {
+  if (init_random) {  // each graph from the start of its own stream, as fa_host
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int g = 0; g < count; ++g)
+      uniform_stream(seeds ? seeds[g] : p.seed, (size_t)(off[g + 1] - off[g]) * dim,
+                     X + (size_t)off[g] * dim);
+  }
+  fa_batch_device(ctx, count, off, ip, ix, dx, dim, X, iterations, p);
+  if (p.normalize)
+    for (int g = 0; g < count; ++g)
+      if (off[g + 1] > off[g]) normalize_host(X + (size_t)off[g] * dim, off[g + 1] - off[g], dim);
+}
+
+// anyToMultilevel(forceAtlas) (src/embed.cpp:23-83 over include/forceatlas.hpp:307-312):
+// every aggregate's internal entries as one block of a block-diagonal CSR (rows in P_T
+// order, columns by position in the P_T row, ascending, duplicates summed as
+// CooMatrix::ToSparse does, 1.0 per stored entry), one batch, then the placement of :66-82.
+// local_of[v]: v's position in its aggregate's row of P_T.
+void fa_ml_batch_host(ge_ctx* ctx, int n, const int* I, const int* J, int m, const int* PI,
+                      const int* PJ, const int* vA, const int* local_of, const double* cA,
+                      const double* rA, int dim, int iterations, const ge_fa_params& p,
+                      double* coords) {
+  std::vector<int> ci(n + 1, 0), cj;
+  std::vector<double> cd;
+  std::vector<int> row;
+  for (int a = 0; a < m; ++a)
+    for (int c = PI[a]; c < PI[a + 1]; ++c) {
+      const int v = PJ[c];
+      row.clear();
+      for (int kk = I[v]; kk < I[v + 1]; ++kk)
+        if (vA[J[kk]] == a) row.push_back(PI[a] + local_of[J[kk]]);
+      std::sort(row.begin(), row.end());
+      for (size_t q = 0; q < row.size(); ++q) {
+        if (q > 0 && row[q] == row[q - 1]) {
+          cd.back() += 1.0;
+        } else {
+          cj.push_back(row[q]);
+          cd.push_back(1.0);
+        }
+      }
+      ci[c + 1] = (int)cj.size();
+    }
+  if (cj.empty()) {  // DevCsr and the checks want arrays
+    cj.push_back(0);
+    cd.push_back(0.0);
+  }
+  std::vector<double> X((size_t)n * dim);
+  fa_batch_host(ctx, m, PI, ci.data(), cj.data(), cd.data(), dim, X.data(), true, nullptr,
+                iterations, p);
+  for (int a = 0; a < m; ++a) {
+    double mx = 0.0;
+    for (int c = PI[a]; c < PI[a + 1]; ++c) {
+      const double mg = norm_of(X.data() + (size_t)c * dim, dim);
+      if (mg > mx) mx = mg;
+    }
+    for (int c = PI[a]; c < PI[a + 1]; ++c)
+      for (int k = 0; k < dim; ++k)
+        coords[(size_t)PJ[c] * dim + k] = cA[(size_t)a * dim + k] + rA[a] * (X[(size_t)c * dim + k] / mx);
+  }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
 // embed orchestration (src/embed.cpp:561-796): the coarsest level's forceAtlas
 // (:586), then per finer level the radius step (:615-777) and
 // forceAtlasMultilevel (:793).  With a communicator of more than one rank the
@@ -472,6 +568,63 @@ int ge_force_atlas(ge_ctx* ctx, int n, const int* ip, const int* ix, const doubl
     ge::check_csr(n, ip, ix, dx);
     ge::DeviceGuard g(ctx);
     ge::fa_host(ctx, n, ip, ix, dx, dim, coords, init_random != 0, iterations, *p);
+  });
+}
+
+// The argument checks come before the context is looked at: they need no device.
+int ge_force_atlas_batch(ge_ctx* ctx, int count, const int* off, const int* ip, const int* ix,
+                         const double* dx, int dim, double* coords, int init_random,
+                         const unsigned* seeds, int iterations, const ge_fa_params* p) {
+  return guarded([&] {
+    GE_REQUIRE(p, "null argument");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
+    GE_REQUIRE(iterations >= 0, "negative iteration count");
+    ge::check_batch(count, off, ip, ix, dx);
+    GE_REQUIRE(ctx, "null context");
+    GE_REQUIRE(coords || count == 0 || off[count] == 0, "null argument");
+    ge::DeviceGuard g(ctx);
+    ge::fa_batch_host(ctx, count, off, ip, ix, dx, dim, coords, init_random != 0, seeds,
+                      iterations, *p);
+  });
+}
+
+int ge_embed_via_force_atlas_ml(ge_ctx* ctx, int n, const int* ip, const int* ix, int m,
+                                const int* pip, const int* pix, const int* vA, const double* cA,
+                                const double* rA, int dim, int iterations, const ge_fa_params* p,
+                                double* coords, int* totals) {
+  return guarded([&] {
+    GE_REQUIRE(p, "null argument");
+    GE_REQUIRE(n >= 0 && m >= 0, "negative size");
+    GE_REQUIRE(dim >= 1 && dim <= 16, "dimension must be 1..16");
+    GE_REQUIRE(iterations >= 0, "negative iteration count");
+    if (totals) std::fill(totals, totals + GE_FA_BATCH_TOTALS, 0);
+    GE_REQUIRE(pip && pip[0] == 0, "null or bad P_T indptr");
+    for (int a = 0; a < m; ++a) GE_REQUIRE(pip[a + 1] >= pip[a], "P_T indptr decreases");
+    GE_REQUIRE(pip[m] == n, "P_T must have one entry per fine vertex");
+    std::vector<int> local_of(n, -1);
+    if (n > 0) {
+      GE_REQUIRE(ip && ix && pix && vA && cA && rA && coords, "null argument");
+      GE_REQUIRE(ip[0] == 0, "bad indptr");
+      for (int i = 0; i < n; ++i) {
+        GE_REQUIRE(ip[i + 1] >= ip[i], "indptr decreases");
+        for (int kk = ip[i]; kk < ip[i + 1]; ++kk)
+          GE_REQUIRE((unsigned)ix[kk] < (unsigned)n, "column index out of range");
+      }
+      // P_T is a partition of the fine vertices and vertex_A is its inverse
+      for (int a = 0; a < m; ++a)
+        for (int c = pip[a]; c < pip[a + 1]; ++c) {
+          const int v = pix[c];
+          GE_REQUIRE((unsigned)v < (unsigned)n && local_of[v] < 0,
+                     "P_T must list every fine vertex once");
+          GE_REQUIRE(vA[v] == a, "vertex_A does not match P_T");
+          local_of[v] = c - pip[a];
+        }
+    }
+    GE_REQUIRE(ctx, "null context");
+    ge::DeviceGuard g(ctx);
+    ge::fa_ml_batch_host(ctx, n, ip, ix, m, pip, pix, vA, local_of.data(), cA, rA, dim, iterations,
+                         *p, coords);
+    if (totals) std::copy(ctx->fa_batch, ctx->fa_batch + GE_FA_BATCH_TOTALS, totals);
   });
 }
 

@@ -178,6 +178,7 @@ struct ge_ctx {
   struct {
     int rounds = 0, max_pops = 0;
   } radius;
+  int fa_batch[GE_FA_BATCH_TOTALS] = {0, 0, 0, 0};  // ge_fa_batch_info
 };
 
 // A communicator (ge_dist.hip): RCCL, or a caller transport staged through host
@@ -251,6 +252,16 @@ int sym_blocks_per_cu(int dim);
 void fa_run_device(ge_ctx* ctx, int n, int nnz, const int* d_ip, const int* d_ix,
                    const double* d_dx, int dim, double* d_x, int iterations,
                    const ge_fa_params& p);
+// deg + 1 of n rows (degp1_kernel, ge_fa.hip) on stream s.
+void launch_degp1(hipStream_t s, int n, const int* d_ip, const double* d_dx, int use_weights,
+                  double* d_dp1);
+// The device part of ge_force_atlas_batch on validated host arrays (ge_fa_batch.hip): the
+// iterations of every graph of the block-diagonal CSR on X (N*dim, in/out) -- the wave
+// and block launches, then the serial graphs through fa_run_device -- and the class
+// totals into ctx->fa_batch.  The initial draw and normalize are the caller's.
+void fa_batch_device(ge_ctx* ctx, int count, const int* off, const int* ip, const int* ix,
+                     const double* dx, int dim, double* X, int iterations,
+                     const ge_fa_params& p);
 // The layout energy on a plan (ge_fa.hip over ge_energy.hip): the five columns of the
 // plan's rows into d_rows (device; nullptr: the plan's own buffer, returned) on its
 // stream, and the column sums of `rows` rows of d_rows into totals (host, 5;

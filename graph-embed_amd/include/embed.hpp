@@ -7,7 +7,8 @@
 // available.  Both print the reference's "embedding layer" lines.
 // The alternative embedders (embedViaMinimization, anyToMultilevel, embedVia,
 // embedViaMultilevel, src/embed.cpp:23-559) are implemented at the end, with
-// minimizationToMultilevel: anyToMultilevel(embedViaMinimization) as one device call.
+// minimizationToMultilevel: anyToMultilevel(embedViaMinimization) as one device call,
+// and forceAtlasToMultilevel: anyToMultilevel(forceAtlas) as one batched device call.
 #ifndef EMBED_HPP
 #define EMBED_HPP
 
@@ -209,6 +210,34 @@ inline MultilevelEmbedder minimizationToMultilevel(int ITER = 1000) {
         detail::context(), n, A.GetIndptr().data(), A.GetIndices().data(), m,
         P_T.GetIndptr().data(), P_T.GetIndices().data(), v_A.data(), cA.data(), r_A.data(), d,
         ITER, X.data(), nullptr));
+    detail::unflatten(X, n, d, coords);
+  };
+}
+
+// anyToMultilevel([](const SparseMatrix& A, int d) { return forceAtlas(A, d); }) with
+// `iterations` in place of forceAtlas(A, d)'s 100000, as one libge call
+// (ge_embed_via_force_atlas_ml): every aggregate of the level in one batched device
+// call with the parameters, seed and mode of forceAtlas(A, d), the same bits as the
+// composition.  Opt-in, like minimizationToMultilevel.
+inline MultilevelEmbedder forceAtlasToMultilevel(int iterations = 100000) {
+  return [iterations](const SparseMatrix& A, const SparseMatrix& P_T, const std::vector<int>& v_A,
+                      const std::vector<std::vector<double>>& coords_A,
+                      const std::vector<double>& r_A, std::vector<std::vector<double>>& coords,
+                      const int d) {
+    const int n = A.Rows(), m = P_T.Rows();
+    if ((int)v_A.size() != n || (int)r_A.size() != m || (int)coords_A.size() != m)
+      throw std::invalid_argument("forceAtlasToMultilevel: sizes do not match A and P_T");
+    ge_fa_params p;
+    ge_fa_params_default(&p);
+    p.seed = detail::seed_ref();
+    p.mode = detail::mode_ref();
+    p.theta = detail::theta_ref();
+    const std::vector<double> cA = detail::flatten(coords_A, m, d);
+    std::vector<double> X((size_t)n * d);
+    detail::check(ge_embed_via_force_atlas_ml(
+        detail::context(), n, A.GetIndptr().data(), A.GetIndices().data(), m,
+        P_T.GetIndptr().data(), P_T.GetIndices().data(), v_A.data(), cA.data(), r_A.data(), d,
+        iterations, &p, X.data(), nullptr));
     detail::unflatten(X, n, d, coords);
   };
 }

@@ -79,6 +79,68 @@ inline std::vector<std::vector<double>> forceAtlas(const SparseMatrix& A, const 
   return coords;
 }
 
+// An addition: the reference has no such function.  forceAtlas on every graph of `As` in
+// one device call (ge_force_atlas_batch): coords[g] ends with the bits of
+// forceAtlas(As[g], dim, coords[g], ...) alone.  An empty coords draws every graph's
+// start from mt19937(seed), as forceAtlas does for an empty coords; otherwise it holds
+// one n_g x dim start per graph.
+inline void forceAtlasBatch(const std::vector<SparseMatrix>& As, const int dim,
+                            std::vector<std::vector<std::vector<double>>>& coords,
+                            const int iterations = 100000, const double ks = 0.1,
+                            const double ksmax = 1.0, const double repel = 1.0,
+                            const double attract = 1.0, const double gravity = 1.0,
+                            const bool useWeights = true, const bool linlog = false,
+                            const bool nohubs = false, const double delta = 1.0,
+                            const double tolerate = 1.0, const bool normalize = false) {
+  ge_fa_params p;
+  ge_fa_params_default(&p);
+  p.ks = ks;
+  p.ksmax = ksmax;
+  p.repel = repel;
+  p.attract = attract;
+  p.gravity = gravity;
+  p.use_weights = useWeights;
+  p.linlog = linlog;
+  p.nohubs = nohubs;
+  p.delta = delta;
+  p.tolerate = tolerate;
+  p.normalize = normalize;
+  p.seed = detail::seed_ref();
+  p.mode = detail::mode_ref();
+  p.theta = detail::theta_ref();
+  const int count = (int)As.size();
+  const bool init = coords.empty();
+  if (!init && (int)coords.size() != count)
+    throw std::invalid_argument("forceAtlasBatch: one coordinate set per graph");
+  std::vector<int> off(count + 1, 0), ip(1, 0), ix;
+  std::vector<double> dx, X;
+  for (int g = 0; g < count; ++g) {
+    const SparseMatrix& A = As[g];
+    const int n = A.Rows(), e0 = (int)ix.size();
+    for (int i = 0; i < n; ++i) ip.push_back(e0 + A.GetIndptr()[i + 1]);
+    for (int j : A.GetIndices()) ix.push_back(off[g] + j);
+    dx.insert(dx.end(), A.GetData().begin(), A.GetData().end());
+    off[g + 1] = off[g] + n;
+    const std::vector<double> x =
+        init ? std::vector<double>((size_t)n * dim) : detail::flatten(coords[g], n, dim);
+    X.insert(X.end(), x.begin(), x.end());
+  }
+  if (ix.empty()) {  // the ABI wants arrays
+    ix.push_back(0);
+    dx.push_back(0.0);
+  }
+  if (X.empty()) X.push_back(0.0);
+  detail::check(ge_force_atlas_batch(detail::context(), count, off.data(), ip.data(), ix.data(),
+                                     dx.data(), dim, X.data(), init ? 1 : 0, nullptr, iterations,
+                                     &p));
+  coords.resize(count);
+  for (int g = 0; g < count; ++g) {
+    const std::vector<double> x(X.begin() + (size_t)off[g] * dim,
+                                X.begin() + (size_t)off[g + 1] * dim);
+    detail::unflatten(x, off[g + 1] - off[g], dim, coords[g]);
+  }
+}
+
 inline void forceAtlasMultilevel(const SparseMatrix& A, const SparseMatrix& P,
                                  const std::vector<int>& v_A,
                                  const std::vector<std::vector<double>>& coords_A,

@@ -97,6 +97,16 @@ _SIGS = {
                                          ctypes.POINTER(FaParams), ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, _ip]),
     "ge_fa_plan_schedule": (ctypes.c_int, [_vp, _ip]),
+    "ge_force_atlas_batch": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p,
+                                            ctypes.c_int, _f64p, ctypes.c_int, _vp, ctypes.c_int,
+                                            ctypes.POINTER(FaParams)]),
+    "ge_fa_batch_sched_query": (ctypes.c_int, [ctypes.c_int, _i32p, _i32p, ctypes.c_int,
+                                               ctypes.POINTER(FaParams), _i32p, _i32p, _ip]),
+    "ge_fa_batch_info": (ctypes.c_int, [_vp, _ip]),
+    "ge_embed_via_force_atlas_ml": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int,
+                                                   _i32p, _i32p, _i32p, _f64p, _f64p,
+                                                   ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(FaParams), _f64p, _ip]),
     "ge_fa_plan_destroy": (ctypes.c_int, [_vp]),
     "ge_force_atlas_ml": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
                                          _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, ctypes.c_int,
@@ -380,6 +390,14 @@ class Context:
 
     def embed_via_minimization_ml(self, A, PT, vertex_A, coords_A, r_A, dim, **kw):
         return embed_via_minimization_ml(A, PT, vertex_A, coords_A, r_A, dim, ctx=self, **kw)
+
+    def force_atlas_batch(self, graphs, dim, coords=None, iterations=100000, seeds=None,
+                          info=False, **kw):
+        return force_atlas_batch(graphs, dim, coords=coords, iterations=iterations, seeds=seeds,
+                                 info=info, ctx=self, **kw)
+
+    def embed_via_force_atlas_ml(self, A, PT, vertex_A, coords_A, r_A, dim, **kw):
+        return embed_via_force_atlas_ml(A, PT, vertex_A, coords_A, r_A, dim, ctx=self, **kw)
 
     def modularity(self, A, vertex_A, m):
         """partition::modularity with the O(nnz) pass on the device
@@ -922,6 +940,118 @@ def fa_schedule(n, dim, cus, rb=0, re=None, iterations=0, nnz=0, masses_ok=True,
     _check(lib().ge_fa_sched_query(n, rb, n if re is None else re, dim, ctypes.byref(p), cus, nnz,
                                    iterations, int(masses_ok), out))
     return _fa_sched_dict(FA_SCHED_SCALARS, out)
+
+
+FA_BATCH_CLASSES = ("wave", "block", "serial")  # GE_FA_BATCH_*
+FA_BATCH_TOTALS = ("waves", "blocks", "serials", "wave_workgroups")
+
+
+def fa_batch_schedule(sizes, entries, dim, **params_kw):
+    """The batch schedule (ge_fa_batch_sched_query; fa_batch_schedule in
+    graph-embed_amd/csrc/ge_fa_sched.hpp) with no device touched, under the knobs now in
+    the environment: per graph of sizes[g] rows and entries[g] stored entries its class
+    (0 wave, 1 block, 2 serial: FA_BATCH_CLASSES) and lanes per row (0: serial), and the
+    totals of FA_BATCH_TOTALS."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    entries = np.ascontiguousarray(entries, dtype=np.int32)
+    if sizes.shape != entries.shape or sizes.ndim != 1:
+        raise ValueError("sizes and entries must be 1-D and of one length")
+    cls, lanes = np.zeros(len(sizes), dtype=np.int32), np.zeros(len(sizes), dtype=np.int32)
+    totals = (ctypes.c_int * len(FA_BATCH_TOTALS))()
+    p = params(**params_kw)
+    _check(lib().ge_fa_batch_sched_query(len(sizes), sizes, entries, dim, ctypes.byref(p), cls,
+                                         lanes, totals))
+    return {"cls": cls, "lanes": lanes, **dict(zip(FA_BATCH_TOTALS, totals))}
+
+
+def concat_graphs(graphs):
+    """A list of CSR matrices as the block-diagonal CSR of ge_force_atlas_batch:
+    (off, indptr, indices, data) with graph g on rows and columns [off[g], off[g+1])."""
+    gs = [_csr(A) for A in graphs]
+    off = np.zeros(len(gs) + 1, dtype=np.int64)
+    eoff = np.zeros(len(gs) + 1, dtype=np.int64)
+    for g, (ip, ix, _) in enumerate(gs):
+        off[g + 1] = off[g] + len(ip) - 1
+        eoff[g + 1] = eoff[g] + len(ix)
+    ip = np.concatenate([np.zeros(1, dtype=np.int64)] +
+                        [a[0][1:].astype(np.int64) + eoff[g] for g, a in enumerate(gs)])
+    ix = np.concatenate([np.zeros(0, dtype=np.int64)] +
+                        [a[1].astype(np.int64) + off[g] for g, a in enumerate(gs)])
+    dx = np.concatenate([np.zeros(0)] + [a[2] for a in gs])
+    return (off.astype(np.int32), ip.astype(np.int32), ix.astype(np.int32),
+            np.ascontiguousarray(dx, dtype=np.float64))
+
+
+def force_atlas_batch(graphs, dim, coords=None, iterations=100000, seeds=None, info=False,
+                      ctx=None, **kw):
+    """ge_force_atlas_batch: forceAtlas on every CSR matrix of `graphs` in one device call,
+    each with the bits of Context.force_atlas on it alone.  coords: a list of n_g x dim
+    arrays (None: every graph draws its start from mt19937(seeds[g]), or from
+    mt19937(seed) when seeds is None).  Returns the list of coordinates; info=True also
+    the class totals (FA_BATCH_TOTALS) of the call.  ctx=None only checks the arguments
+    (the library then reports the missing context)."""
+    off, ip, ix, dx = concat_graphs(graphs)
+    N = int(off[-1])
+    if coords is None:
+        X = np.zeros((N, dim))
+    else:
+        if len(coords) != len(graphs):
+            raise ValueError("one coordinate array per graph")
+        X = np.concatenate([np.zeros((0, dim))] + [
+            np.asarray(c, dtype=np.float64).reshape(-1, dim) for c in coords])
+        if len(X) != N:
+            raise ValueError("coordinates must be n_g x dim per graph")
+    X = np.ascontiguousarray(X)
+    sd = None
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if len(sd) != len(graphs):
+            raise ValueError("one seed per graph")
+    out = _force_atlas_batch_raw(ctx, off, ip, ix, dx, dim, X, coords is None, sd, iterations, kw)
+    res = [out[off[g]:off[g + 1]] for g in range(len(graphs))]
+    if not info:
+        return res
+    totals = (ctypes.c_int * len(FA_BATCH_TOTALS))()
+    _check(lib().ge_fa_batch_info(ctx.h, totals))
+    return res, dict(zip(FA_BATCH_TOTALS, totals))
+
+
+def _force_atlas_batch_raw(ctx, off, ip, ix, dx, dim, X, init_random, seeds, iterations, kw):
+    """ge_force_atlas_batch on the block-diagonal arrays as given (the tests' error cases)."""
+    p = params(**kw)
+    _check(lib().ge_force_atlas_batch(
+        ctx.h if ctx is not None else None, len(off) - 1, off, ip, ix, dx, dim, X.reshape(-1),
+        int(init_random), seeds.ctypes.data if seeds is not None else None, iterations,
+        ctypes.byref(p)))
+    return X
+
+
+def embed_via_force_atlas_ml(A, PT, vertex_A, coords_A, r_A, dim, iterations=100000, ctx=None,
+                             info=False, **kw):
+    """anyToMultilevel(forceAtlas) on one level (src/embed.cpp:23-83 over
+    include/forceatlas.hpp:307-312) as one ge_embed_via_force_atlas_ml call: per
+    aggregate of PT, forceAtlas from the random start of mt19937(seed) on the members'
+    internal entries, normalised by its largest norm and placed in the aggregate's ball.
+    info=True also returns the batch's class totals (FA_BATCH_TOTALS)."""
+    ip = np.ascontiguousarray(A[0], dtype=np.int32)
+    ix = np.ascontiguousarray(A[1], dtype=np.int32)
+    pip = np.ascontiguousarray(PT[0], dtype=np.int32)
+    pix = np.ascontiguousarray(PT[1], dtype=np.int32)
+    n, m = len(ip) - 1, len(pip) - 1
+    vA = np.ascontiguousarray(vertex_A, dtype=np.int32)
+    cA = np.ascontiguousarray(coords_A, dtype=np.float64).reshape(-1)
+    rA = np.ascontiguousarray(r_A, dtype=np.float64).reshape(-1)
+    if len(vA) != n or len(cA) != m * dim or len(rA) != m or len(pix) != n:
+        raise GeError("embed_via_force_atlas_ml: array sizes do not match n, m and dim")
+    X = np.zeros((n, dim))
+    totals = (ctypes.c_int * len(FA_BATCH_TOTALS))()
+    p = params(**kw)
+    _check(lib().ge_embed_via_force_atlas_ml(ctx.h if ctx is not None else None, n, ip, ix, m, pip,
+                                             pix, vA, cA, rA, dim, iterations, ctypes.byref(p),
+                                             X.reshape(-1), totals))
+    if not info:
+        return X
+    return X, dict(zip(FA_BATCH_TOTALS, totals))
 
 
 class FaPlan:

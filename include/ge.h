@@ -316,6 +316,62 @@ int ge_fa_sched_query(int n, int row_begin, int row_end, int dim, const ge_fa_pa
 int ge_fa_plan_schedule(ge_fa_plan* plan, int* out);
 int ge_fa_plan_destroy(ge_fa_plan* plan);
 
+/* ---- many small graphs in one call ----
+ * count independent graphs as one block-diagonal CSR: graph g owns rows and
+ * columns [off[g], off[g+1]) of N = off[count] vertices.  coords: N*dim in/out.
+ * init_random != 0: graph g draws its n_g*dim values from the START of
+ * mt19937(seeds ? seeds[g] : p->seed), as a separate ge_force_atlas call would.
+ * Contract: for every graph and in every mode the result has the bits of
+ * ge_force_atlas on that graph alone with the same parameters and that graph's seed.
+ * p->normalize is applied per graph.  The result of a graph does not depend on where
+ * it stands in the batch or on what else is in it.  Empty graphs (n_g = 0) and
+ * count = 0 are fine.  GE_ERR_ARG, with a message that names the graph: offsets that do
+ * not ascend from 0, an entry whose column lies outside its graph's block, and, with no
+ * graph to name, dim outside 1..16 and negative iterations.
+ * Each graph runs in one of three classes, decided on the host
+ * (graph-embed_amd/csrc/ge_fa_sched.hpp, fa_batch_schedule):
+ *   GE_FA_BATCH_WAVE    1 <= n_g <= 64 under GE_MODE_STRICT or the wide schedule
+ *                       (dim >= 5): one wave per graph, 4 graphs per workgroup, the
+ *                       whole class one launch;
+ *   GE_FA_BATCH_BLOCK   up to 512 rows (256 on the wide schedule): one workgroup per
+ *                       graph, one launch;
+ *   GE_FA_BATCH_SERIAL  larger graphs, and every graph under GE_MODE_FAST /
+ *                       GE_MODE_FARFIELD at dim <= 4: ge_force_atlas's own device path, one
+ *                       graph after another inside the call, after the two launches.
+ * ge_fa_batch_sched_query: host only, no device: class and lanes per row (0: serial) of
+ * each graph from its rows (sizes) and stored entries, and totals[GE_FA_BATCH_TOTALS] =
+ * {waves, blocks, serials, workgroups of the wave launch}.  cls, lanes: count ints each;
+ * any of the three may be NULL.  ge_fa_batch_info: the totals of the last
+ * ge_force_atlas_batch / ge_embed_via_force_atlas_ml on ctx. */
+#define GE_FA_BATCH_WAVE 0
+#define GE_FA_BATCH_BLOCK 1
+#define GE_FA_BATCH_SERIAL 2
+#define GE_FA_BATCH_TOTALS 4
+int ge_force_atlas_batch(ge_ctx* ctx, int count, const int* off, const int* indptr,
+                         const int* indices, const double* data, int dim, double* coords,
+                         int init_random, const unsigned* seeds, int iterations,
+                         const ge_fa_params* p);
+int ge_fa_batch_sched_query(int count, const int* sizes, const int* entries, int dim,
+                            const ge_fa_params* p, int* cls, int* lanes, int* totals);
+int ge_fa_batch_info(const ge_ctx* ctx, int* totals);
+
+/* anyToMultilevel(forceAtlas)(A, P_T, v_A, coords_A, r_A, coords, d), src/embed.cpp:23-83
+ * over include/forceatlas.hpp:307-312, as one call: per aggregate of P_T the members'
+ * internal entries as an r x r matrix (1.0 per stored entry, duplicates summed, self
+ * entries kept, rows in P_T order, columns ascending by position in the P_T row), all of
+ * them as one ge_force_atlas_batch with init_random on and p->seed for every aggregate,
+ * each result divided by its largest norm and placed at coords_A[a] + r_A[a] * (x / max).
+ * An aggregate of one member gives what the reference's division gives: its one point,
+ * moved off the origin by gravity, lands on the ball's surface, and a layout that ends at
+ * the origin divides 0 by 0 (NaN).  The weights of A are not read.  P_T must list every fine vertex once and vertex_A must be
+ * its inverse (GE_ERR_ARG otherwise).  totals (may be NULL): as ge_fa_batch_info.
+ * iterations: the reference's forceAtlas(A, d) runs 100000. */
+int ge_embed_via_force_atlas_ml(ge_ctx* ctx, int n, const int* indptr, const int* indices,
+                                int m, const int* pt_indptr, const int* pt_indices,
+                                const int* vertex_A, const double* coords_A, const double* r_A,
+                                int dim, int iterations, const ge_fa_params* p, double* coords,
+                                int* totals);
+
 /* ---- layout energy ----
  * A yardstick for a layout, whatever produced it (graph-embed_amd/csrc/ge_energy.hip;
  * the reference has no such function).  With m_i = deg_i + 1 as the iteration uses it (the
