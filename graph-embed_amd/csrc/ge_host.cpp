@@ -540,6 +540,10 @@ int ge_ctx_destroy(ge_ctx* ctx) {
       (void)hipStreamSynchronize(ctx->own);
       (void)hipStreamDestroy(ctx->own);
     }
+    if (ctx->knn_scratch) {
+      ge::DeviceGuard g(ctx);
+      ge::knn_release(ctx->knn_scratch);
+    }
     delete ctx;
   });
 }

@@ -159,6 +159,10 @@ struct DevCsr {
   }
 };
 
+// The scratch of a context's nearest-neighbour calls (ge_knn.hip), made by the first one.
+struct KnnScratch;
+void knn_release(KnnScratch* s);
+
 }  // namespace ge
 
 struct ge_ctx {
@@ -179,6 +183,11 @@ struct ge_ctx {
     int rounds = 0, max_pops = 0;
   } radius;
   int fa_batch[GE_FA_BATCH_TOTALS] = {0, 0, 0, 0};  // ge_fa_batch_info
+  struct {  // ge_knn_info; the device path's insertions are read from the scratch
+    int path = GE_KNN_PATH_NONE, form = GE_KNN_FORM_NARROW, rows_per_wg = 0, jsplit = 0;
+    long long host_insertions = 0;
+  } knn;
+  ge::KnnScratch* knn_scratch = nullptr;
 };
 
 // A communicator (ge_dist.hip): RCCL, or a caller transport staged through host

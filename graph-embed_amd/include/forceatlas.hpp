@@ -203,6 +203,38 @@ inline std::array<double, GE_ENERGY_COLS> layoutEnergy(
   return totals;
 }
 
+// An addition: the reference has no such function.  The exact k nearest neighbours of
+// every vertex in the layout ("layout neighbours" in include/ge.h), row i in ascending
+// order of (squared distance, index); -1 past the last candidate.  1 <= k <= GE_KNN_MAX_K.
+inline std::vector<std::vector<int>> layoutNeighbours(
+    const std::vector<std::vector<double>>& coords, const int k) {
+  const int n = (int)coords.size();
+  const int dim = coords.empty() ? 0 : (int)coords[0].size();
+  std::vector<double> X = detail::flatten(coords, n, dim);
+  std::vector<int> idx((size_t)n * (k > 0 ? k : 0));
+  detail::check(ge_layout_knn(detail::context(), n, dim, X.data(), k, n, nullptr, idx.data(),
+                              nullptr));
+  std::vector<std::vector<int>> out(n);
+  for (int i = 0; i < n; ++i)  // check() has thrown unless 1 <= k
+    out[i].assign(idx.begin() + (size_t)i * k, idx.begin() + (size_t)(i + 1) * k);
+  return out;
+}
+
+// An addition.  The neighbourhood precision of the layout on graph A (ascending rows):
+// the totals {rows with a neighbour, sum k_i, sum hits_i} (GE_NBHD_*) over all vertices,
+// k_i = min(distinct neighbours of i, kmax); the pooled score is [2] / [1].
+inline std::array<long long, GE_NBHD_TOTALS> neighbourhoodPrecision(
+    const SparseMatrix& A, const std::vector<std::vector<double>>& coords, const int kmax = 16) {
+  const int n = A.Rows();
+  const int dim = coords.empty() ? 0 : (int)coords[0].size();
+  std::vector<double> X = detail::flatten(coords, n, dim);
+  std::array<long long, GE_NBHD_TOTALS> totals{};
+  detail::check(ge_layout_neighbourhood(detail::context(), n, A.GetIndptr().data(),
+                                        A.GetIndices().data(), dim, X.data(), kmax, n, nullptr,
+                                        nullptr, totals.data()));
+  return totals;
+}
+
 }  // namespace partition
 
 #endif  // FORCEATLAS_HPP

@@ -35,6 +35,13 @@ FAR_MAX_LEVELS = 8  # GE_FAR_MAX_LEVELS
 # the columns of the layout energy (GE_ENERGY_*, include/ge.h)
 ENERGY_COLS = 5
 ENERGY_REP, ENERGY_ATT, ENERGY_GRAV, ENERGY_PAIRDIST, ENERGY_EDGELEN = range(ENERGY_COLS)
+# layout neighbours (include/ge.h): GE_KNN_MAX_K, the totals of the neighbourhood
+# precision (GE_NBHD_*) and ge_knn_info's codes (GE_KNN_PATH_*, GE_KNN_FORM_*)
+KNN_MAX_K = 64
+NBHD_TOTALS = 3
+NBHD_ROWS, NBHD_K, NBHD_HITS = range(NBHD_TOTALS)
+KNN_PATHS = ("none", "host", "device")
+KNN_FORMS = ("narrow", "wide")
 # ge_fa_plan_far_info reason codes (GE_FAR_*)
 FAR_REASONS = ("active", "not_requested", "dim", "row_shard", "mass", "small")
 # GE_ROW_*: how the last row pass finished a heavy row (FaPlan.rows_info)
@@ -81,6 +88,14 @@ _SIGS = {
     "ge_fa_plan_energy": (ctypes.c_int, [_vp, _vp, _vp, _f64p]),
     "ge_layout_energy": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _f64p, ctypes.c_int,
                                         _f64p, ctypes.POINTER(FaParams), _vp, _f64p]),
+    "ge_layout_knn": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_int,
+                                     ctypes.c_int, _vp, _vp, _vp]),
+    "ge_layout_knn_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                            ctypes.c_int, _vp, _vp, _vp]),
+    "ge_layout_neighbourhood": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int,
+                                               _f64p, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                               ctypes.POINTER(ctypes.c_longlong)]),
+    "ge_knn_info": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip, ctypes.POINTER(ctypes.c_longlong)]),
     "ge_fa_plan_rows_info": (ctypes.c_int, [_vp, _ip, _vp, _vp]),
     "ge_fa_plan_far_info": (ctypes.c_int, [_vp, _ip, _ip, ctypes.POINTER(ctypes.c_double), _ip, _ip,
                                            _ip, ctypes.POINTER(ctypes.c_longlong), _ip,
@@ -329,6 +344,66 @@ def relative_edge_length(totals, n, nnz):
     return (totals[ENERGY_EDGELEN] / nnz) / (totals[ENERGY_PAIRDIST] / (n * (n - 1.0)))
 
 
+def _knn_args(X, rows):
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"coordinates must be n x dim, got {X.shape}")
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    return X, rows, (X.shape[0] if rows is None else len(rows))
+
+
+def layout_knn(X, k, rows=None, dist=False, ctx=None):
+    """The exact k nearest neighbours of the query rows in the layout X (ge_layout_knn,
+    "layout neighbours" in include/ge.h): idx (n_rows x k int32; -1 past the last
+    candidate), in ascending order of (squared distance, index); with dist=True also the
+    squared distances (+inf past the last candidate).  rows=None asks for every row;
+    otherwise ids in any order, repeats allowed.  With a Context the pass runs on the
+    device; without one (or GE_KNN_HOST=1) on the library's host path, with the same
+    bits."""
+    X, rows, n_rows = _knn_args(X, rows)
+    k = int(k)
+    idx = np.empty((n_rows, max(k, 0)), dtype=np.int32)
+    d2 = np.empty((n_rows, max(k, 0))) if dist else None
+    _check(lib().ge_layout_knn(ctx.h if ctx is not None else None, X.shape[0], X.shape[1],
+                               X.reshape(-1), k, n_rows,
+                               rows.ctypes.data if rows is not None else None, idx.ctypes.data,
+                               d2.ctypes.data if dist else None))
+    return (idx, d2) if dist else idx
+
+
+def layout_neighbourhood(A, X, kmax=16, rows=None, ctx=None):
+    """The neighbourhood precision's integers (ge_layout_neighbourhood): per query row
+    {k_i, hits_i} (n_rows x 2 int32) and the totals (3 int64, NBHD_ROWS / NBHD_K /
+    NBHD_HITS); neighbourhood_precision turns either into the score.  The rows of A must
+    be ascending; its weights are not read."""
+    ip = np.ascontiguousarray(A[0], dtype=np.int32)
+    ix = np.ascontiguousarray(A[1], dtype=np.int32)
+    X, rows, n_rows = _knn_args(X, rows)
+    if X.shape[0] != len(ip) - 1:
+        raise ValueError(f"coordinates must be n x dim with n = {len(ip) - 1}, got {X.shape}")
+    per_row = np.empty((n_rows, 2), dtype=np.int32)
+    totals = (ctypes.c_longlong * NBHD_TOTALS)()
+    _check(lib().ge_layout_neighbourhood(ctx.h if ctx is not None else None, X.shape[0], ip, ix,
+                                         X.shape[1], X.reshape(-1), int(kmax), n_rows,
+                                         rows.ctypes.data if rows is not None else None,
+                                         per_row.ctypes.data, totals))
+    return per_row, np.array(list(totals), dtype=np.int64)
+
+
+def neighbourhood_precision(per_row):
+    """(mean, pooled) of layout_neighbourhood's per-row integers: the mean of hits_i / k_i
+    over the rows with k_i > 0, and sum hits_i / sum k_i.  1 when every vertex has its
+    graph neighbours nearest, about k / (n - 1) for a random layout; (nan, nan) when no
+    row has a neighbour."""
+    per_row = np.asarray(per_row).reshape(-1, 2)
+    k, hits = per_row[:, 0].astype(np.int64), per_row[:, 1].astype(np.int64)
+    live = k > 0
+    if not live.any():
+        return float("nan"), float("nan")
+    return float((hits[live] / k[live]).mean()), float(hits.sum() / k.sum())
+
+
 class Context:
     """One device + one HIP stream (ge_ctx)."""
 
@@ -522,6 +597,32 @@ class Context:
         vertex (n x 5; None with rows=False) and their sums (ge_layout_energy).  E is
         totals[ENERGY_REP] + totals[ENERGY_ATT] + totals[ENERGY_GRAV]."""
         return _layout_energy(lib().ge_layout_energy, self.h, A, X, rows, kw)
+
+    def layout_knn(self, X, k, rows=None, dist=False):
+        """layout_knn on the device (ge_layout_knn)."""
+        return layout_knn(X, k, rows=rows, dist=dist, ctx=self)
+
+    def layout_knn_device(self, n, dim, d_x, k, n_rows, d_rows, d_idx, d_dist2=None):
+        """ge_layout_knn_device on device pointers (d_rows and d_dist2 may be None):
+        enqueues on the context's stream and does not synchronise."""
+        _check(lib().ge_layout_knn_device(self.h, n, dim, _vp(d_x), k, n_rows,
+                                          _vp(d_rows) if d_rows else None,
+                                          _vp(d_idx) if d_idx else None,
+                                          _vp(d_dist2) if d_dist2 else None))
+
+    def layout_neighbourhood(self, A, X, kmax=16, rows=None):
+        """layout_neighbourhood with the neighbours from the device."""
+        return layout_neighbourhood(A, X, kmax=kmax, rows=rows, ctx=self)
+
+    def knn_info(self):
+        """The last nearest-neighbour call on this context (ge_knn_info), to be read once
+        its work is complete: the path and kernel form by name, the query rows per
+        workgroup, the j splits and the list insertions summed over the call."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        ins = ctypes.c_longlong(0)
+        _check(lib().ge_knn_info(self.h, *(ctypes.byref(x) for x in v), ctypes.byref(ins)))
+        return {"path": KNN_PATHS[v[0].value], "form": KNN_FORMS[v[1].value],
+                "rows_per_wg": v[2].value, "jsplit": v[3].value, "insertions": ins.value}
 
     def fa_plan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw):
         return FaPlan(self, n, nnz, d_ip, d_ix, d_dx, dim, row_begin, row_end, **kw)

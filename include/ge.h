@@ -430,6 +430,87 @@ int ge_layout_energy(ge_ctx* ctx, int n, const int* indptr, const int* indices,
                      const double* data, int dim, const double* coords, const ge_fa_params* p,
                      double* rows, double* totals);
 
+/* ---- layout neighbours ----
+ * The exact k nearest neighbours of a vertex in a layout, and the neighbourhood precision
+ * built on them: a second yardstick, which sees what the energy's global sums cannot,
+ * whether each vertex still has its own neighbours next to it (graph-embed_amd/csrc/
+ * ge_knn.hip, ge_knn.cpp; the reference has no such function).  Brute force over all
+ * pairs in fp64, by design: it shares no approximation with any mode.
+ *
+ * Squared distance.  s_ij has the form of the energy's pair term: e_k = x_i[k] - x_j[k],
+ * s = e_0 e_0, then s = fma(e_k, e_k, s) for k = 1 .. d-1.  So s_ij and s_ji have the same
+ * bits, and s is +0, positive or not finite.  The run-time-d form (d = 5..16) stores the
+ * coordinates past d as +0 on both sides: the extra fma(0, 0, s) return s unchanged and
+ * the bits are those of a chain of length d.  No square root and no division are taken.
+ *
+ * Candidates of a query row i: every j != i (compared by index) whose s_ij is finite.
+ * Coincident points are candidates with s = 0.  A pair whose s is NaN or +inf is no
+ * candidate in either direction: that covers a NaN or infinite coordinate and squared
+ * differences that overflow, and a query row with such a coordinate has no candidates.
+ *
+ * Neighbours of i: the first min(k, candidates) candidates in ascending order of
+ * (s_ij, j); equal s means the lower index first.  idx[q k + t] is the t-th neighbour of
+ * query row q and dist2[q k + t] its s; the entries past the last candidate are -1 and
+ * +inf.  1 <= k <= GE_KNN_MAX_K.  The order (s, j) is total, so the result is a function
+ * of the coordinates alone: it does not depend on the tiling, the j split, the rows asked
+ * for or the rank that asks.
+ *
+ * rows: NULL means every row (n_rows must then be n); otherwise n_rows >= 0 ids in
+ * [0, n), in any order, repeats allowed, and the output follows the given order.  The
+ * list is how a caller samples rows at a size where n^2 is too much, and how ranks share
+ * the work.
+ *
+ * Neighbourhood precision, for a CSR graph A over the same vertices: g_i = the number of
+ * distinct columns j != i stored in row i, k_i = min(g_i, kmax), hits_i = how many of the
+ * first k_i neighbours of i are columns of row i.  per_row[2 q + {0, 1}] = {k_i, hits_i}
+ * and totals[GE_NBHD_ROWS] = the query rows with k_i > 0, totals[GE_NBHD_K] = sum k_i,
+ * totals[GE_NBHD_HITS] = sum hits_i over the query rows (a repeated id counts each time).
+ * The precision is the mean of hits_i / k_i over the rows with k_i > 0, or pooled,
+ * HITS / K: 1 when every vertex has its graph neighbours nearest, about k / (n - 1) for a
+ * random layout.  Rows of A must be ascending (equal neighbours, that is duplicate
+ * entries, are fine; A need not be symmetric; its weights are not read). */
+#define GE_KNN_MAX_K 64
+#define GE_NBHD_TOTALS 3
+#define GE_NBHD_ROWS 0
+#define GE_NBHD_K 1
+#define GE_NBHD_HITS 2
+#define GE_KNN_PATH_NONE 0 /* no call on this context yet */
+#define GE_KNN_PATH_HOST 1
+#define GE_KNN_PATH_DEVICE 2
+#define GE_KNN_FORM_NARROW 0 /* d <= 4 at compile time */
+#define GE_KNN_FORM_WIDE 1   /* the run-time-d form, d = 5..16 */
+/* coords n*dim, rows n_rows ids or NULL, idx n_rows*k, dist2 n_rows*k or NULL; all host.
+ * ctx == NULL or GE_KNN_HOST=1 takes the library's host path (the plain double loop, the
+ * same bits).  GE_ERR_ARG, with a message that names the range: dim outside 1..16, k
+ * outside 1..64, n < 1, n_rows < 0 (or != n without rows), a row id outside [0, n), null
+ * coords or idx. */
+int ge_layout_knn(ge_ctx* ctx, int n, int dim, const double* coords, int k, int n_rows,
+                  const int* rows, int* idx, double* dist2);
+/* The same on device pointers: enqueues on the context's stream and does not
+ * synchronise.  Needs a context; its scratch belongs to the context and is made by the
+ * first call (a later call that needs more reallocates it).  The ids of d_rows cannot be
+ * checked without waiting: an id outside [0, n) reads nothing and gets no neighbours. */
+int ge_layout_knn_device(ge_ctx* ctx, int n, int dim, const double* d_x, int k, int n_rows,
+                         const int* d_rows, int* d_idx, double* d_dist2);
+/* per_row n_rows*2 ints or NULL, totals GE_NBHD_TOTALS.  The neighbours come from
+ * ge_layout_knn with k = kmax (same paths, same errors; kmax outside 1..64 is
+ * GE_ERR_ARG); a row of A that is not ascending, a bad indptr or a column outside [0, n)
+ * is GE_ERR_ARG with a message that names the row. */
+int ge_layout_neighbourhood(ge_ctx* ctx, int n, const int* indptr, const int* indices, int dim,
+                            const double* coords, int kmax, int n_rows, const int* rows,
+                            int* per_row, long long* totals);
+/* The last call on ctx (diagnostics; no result depends on it): the path (GE_KNN_PATH_*),
+ * the kernel form (GE_KNN_FORM_*), the query rows per workgroup (256, 128 or 64: the most
+ * whose lists of k entries of 12 bytes fit beside the partner tile in half a CU's LDS; 0
+ * on the host path), the j splits (each a chain over ascending j whose sorted partial
+ * lists a second kernel merges under the full order; GE_KNN_JSPLIT = 1..16 forces the
+ * number, read once per call) and the list insertions summed over the call's chains,
+ * counted on the device with one atomic per wave.  Read it once the call's work is
+ * complete: after a host-pointer call returns, or after ge_ctx_sync following
+ * ge_layout_knn_device.  Any pointer may be NULL. */
+int ge_knn_info(const ge_ctx* ctx, int* path, int* form, int* rows_per_wg, int* jsplit,
+                long long* insertions);
+
 /* ---- multilevel ForceAtlas ----
  * Replaces partition::forceAtlasMultilevel(A, P, v_A, coords_A, r_A, coords,
  * dim, iterations, ks, ksmax, useWeights, linlog, nohubs, repel, attract,
